@@ -2,19 +2,26 @@
 """bench.py -- input bytes/s of the whole cmix v21 predictor on enwik8-shaped text, on MI355X.
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it is launched under
-torch.distributed.run, one rank per GPU. Prints ONE JSON line on rank 0.
+torch.distributed.run, one rank per GPU. Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the K steps,
+writes its outputs (--dump-outputs DIR) and prints the line; --full adds everything that is measured or checked beside the
+headline figure (the reference binary on the host cores, the decoder's leg, every rank's own-shard check at N > 1).
 
-Workload (BASELINE.json configs[1], "enwik8 full model ensemble on 1 MI355X", at the size the parity fixture holds):
-rank r compresses the first --payload-bytes (default 1 MiB) of its own S-enwik8 shard (cmix_amd.synth.enwik_like,
+Workload (BASELINE.json configs[1], "enwik8 full model ensemble on 1 MI355X"):
+rank r compresses the first K x --step-bytes (default 64 KiB per step; K = 16 is the 1 MiB the parity fixture holds) of its own S-enwik8 shard (cmix_amd.synth.enwik_like,
 seed 1000 + r, rich alphabet: V = 205 distinct bytes as in enwik8) exactly as `cmix -c` would: the stream the reference's preprocessor hands the predictor (one TEXT
 block), every bit through the FULL ensemble -- all 2078 layer-0 inputs come from engine stages on the GPU (contexts + 54
 small models, LSTM, fxcm's 431 and paq8's 1591 outputs; PPMd and the two text parsers are the engine's host stages,
 inside the timed loop) -- and the final mixing network + SSE, strict bit-exact mode; then the arithmetic coder. A
-"step" is 1/K of the stream (fed in 4 KB sub-chunks so that the stages of consecutive sub-chunks overlap). Inputs are
+"step" is --step-bytes of the stream (the last one also carries the 6 framing bytes), fed in 4 KB sub-chunks so that the stages of consecutive sub-chunks
+overlap: K sets the work timed, and ms_per_step = the time of the K steps + coder / K. Inputs are
 in host memory when the timed region starts (the boundary hands over bytes; 1 byte in, 1 float out per bit crosses
-PCIe); value = stream bytes of all ranks / max-over-ranks time of the K steps + coder. The W warm-up steps run the same
-code on a throw-away engine instance over the head of the same shard. Streams are independent: no
+PCIe); value = stream bytes of all ranks / max-over-ranks time of the K steps + coder. The W warm-up steps (W x --step-bytes) run
+the same code on a throw-away engine instance over the head of the same shard. Streams are independent: no
 collective on the data path ("scaling": "weak").
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path handed its caller, as float32 .npy files: compressed.npy
+(the container bytes finish() returned, one value per byte) and p_last_step.npy (the final probability of every bit of the last
+timed step); an output above 4 Mi values is replaced by the same seeded sample of 4 Mi of its values on every run.
 
 verified: the timed run's OUTPUT FILE (header + code) is compared with the SHA-256 / size of the file the unmodified
 reference binary wrote for the same payload (tests/golden/dropin_*.npz, tests/golden/make_dropin_1m.py) -- compressed
@@ -24,14 +31,14 @@ roofline: per SURVEY.md 8(d): algorithmic HBM bytes of the slowest stage's domin
 `traffic` from the PMC passes committed under profiles/ (read at run time, null when the file is missing).
 end_to_end: the second figure SURVEY.md 8d asks for -- payload bytes / (engine construction + framing + the timed run);
 the warm-up engine's run is NOT in it (round 3 counted it as construction).
-cpu_baseline (kind "reference"): the unmodified reference binary (oracle/_ref/cmix_O3) on a BOUNDED PREFIX of the SAME payload --
+cpu_baseline (--full; kind "reference"): the unmodified reference binary (oracle/_ref/cmix_O3) on a BOUNDED PREFIX of the SAME payload --
 its first --cpu-baseline-bytes (default 128 KB; the whole 1 MiB costs the reference ~55 minutes, the bench contract asks for a
 bounded sample; `config.cpu_baseline_rule` states the rule in the line) --, `-c` (the GPU run's mode, end to end) and `-n` (no
 preprocessing: predictor only), each minus a 256-byte run (construction), each on its own pinned host core, running WHILE the
 GPU run is timed (the bench thread is kept off those cores; `cpu_baseline.concurrent_with_gpu_run` says so; --cpu-baseline-serial
 runs it after the timed section instead, +3 minutes). The reference slows down by ~10 % between 128 KB and 1 MiB as its tables
 fill (tests/golden fixtures' ref_seconds), so the prefix figure flatters the reference, not the engine.
-At N > 1 every rank also verifies ITS OWN shard: after the timed run it codes the first 128 KB of its shard on a fresh engine and
+With --full at N > 1 every rank also verifies ITS OWN shard: after the timed run it codes the first 128 KB of its shard on a fresh engine and
 compares the file with the reference binary's for that seed (tests/golden/dropin_rich_128k_s<seed>.npz); rank 0 reports all ranks.
 --tolerance: the mixing network's tolerance mode (an explicit API switch; not bit-exact; `config.mode` comes from the library).
 """
@@ -102,12 +109,20 @@ print(json.dumps({{"bytes": length, "seconds": t3 - t2, "startup_s": (t1 - t0) -
 '''
 
 
+def _env_int(name):
+    try:
+        return int(os.environ.get(name, ""))
+    except ValueError:
+        return 0
+
+
 def decode_leg(payload, nbytes, dev):
     """the decoder's form of the engine (late-bit protocol) on the head of the same shard, in a child process (a decoder needs
-    every stage kernel of the stream co-resident from its first bit: a fresh process): the look-ahead engine codes the first nbytes, cmx_decode_stream decodes the
-    code; marginal time per byte = (whole - a 64-byte run) / the bytes between."""
+    every stage kernel of the stream co-resident from its first bit: a fresh process, with a hardware queue per stage stream even where the environment asks
+    for fewer): the look-ahead engine codes the first nbytes, cmx_decode_stream decodes the code; marginal time per byte = (whole - a 64-byte run) / the bytes between."""
     try:
-        r = subprocess.run([sys.executable, "-c", _DECODE_CHILD.format(root=ROOT, n=nbytes, seed=1000, dev=dev)], capture_output=True, text=True, timeout=300)
+        r = subprocess.run([sys.executable, "-c", _DECODE_CHILD.format(root=ROOT, n=nbytes, seed=1000, dev=dev)], capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, GPU_MAX_HW_QUEUES=str(max(16, _env_int("GPU_MAX_HW_QUEUES")))))
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if r.returncode != 0 or not line:
             return {"error": (r.stderr or r.stdout)[-300:]}
@@ -224,20 +239,41 @@ class CpuReference:
         return out
 
 
+DUMP_MAX = 4 << 20   # values per dumped output: the two files stay under 64 MB
+
+
+def dump_outputs(d, outputs):
+    """outputs: name -> array; each written as d/<name>.npy in float32, flattened; one longer than DUMP_MAX values is replaced by the
+    same seeded sample of DUMP_MAX of its values on every run (sorted positions)."""
+    os.makedirs(d, exist_ok=True)
+    for name, v in outputs.items():
+        v = np.asarray(v).reshape(-1)
+        if v.size > DUMP_MAX:
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, DUMP_MAX, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), v.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=16, help="timed steps of --step-bytes each (16 x 64 KiB: the 1 MiB of tests/golden/dropin_1m.npz)")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--payload-bytes", type=int, default=1 << 20, help="bytes of the shard each rank compresses (fixtures: 65536, 262144, 1048576)")
+    ap.add_argument("--step-bytes", type=int, default=65536, help="shard bytes per step, a whole number of sub-chunks; each rank compresses the first "
+                    "steps x step-bytes bytes of its shard")
     ap.add_argument("--sub-chunk", type=int, default=4096, help="bytes per pipeline submit (stages of consecutive sub-chunks overlap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the reference binary on the host "
+                    "cores (cpu_baseline), the decoder's leg (decode), and at N > 1 every rank's own-shard file check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the timed path's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the reference binary")
     ap.add_argument("--cpu-baseline-bytes", type=int, default=131072)
     ap.add_argument("--cpu-baseline-serial", action="store_true", help="run the reference binary after the timed section instead of beside it")
-    ap.add_argument("--decode-bytes", type=int, default=4096, help="after the timed run, rank 0 decodes this many bytes of the shard in a child process (cmx_decode_stream over the decoder's "
-                    "form of the engine) and reports `decode`; 0 = skip")
+    ap.add_argument("--decode-bytes", type=int, default=4096, help="with --full: after the timed run, rank 0 decodes this many bytes of the shard in a child process "
+                    "(cmx_decode_stream over the decoder's form of the engine) and reports `decode`; 0 = skip")
     ap.add_argument("--tolerance", action="store_true", help="the mixing network's tolerance mode (NOT bit-exact; the output is not the reference's file)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0 or a.step_bytes < 1 or a.sub_chunk < 1 or a.step_bytes % a.sub_chunk:
+        ap.error("--steps >= 1, --warmup >= 0, and --step-bytes a positive multiple of --sub-chunk")
+    payload_bytes = a.steps * a.step_bytes
 
     import torch
     import torch.distributed as dist
@@ -256,29 +292,29 @@ def main():
         local = 0
     torch.cuda.set_device(local)
 
-    payload = synth.enwik_like(a.payload_bytes, shard.shard_seed(rank), rich=True)
+    payload = synth.enwik_like(payload_bytes, shard.shard_seed(rank), rich=True)
     ncpu = os.cpu_count() or 2
     cpu = None
     # N > 1 (north_star: the reference CPU cmix on the node's own host cores in the same run, at 1 / 2 / 4 / 8 GPUs): one pinned reference process per rank,
     # each on the prefix of ITS rank's shard (`-c`: the GPU run's mode), as many as the host's memory holds at ~32 GB each; rank 0 reports their sum
     # (cores = the number of processes). They run beside the timed GPU run on the highest-numbered cores; the bench threads are kept off those.
     cpu_n = None
-    if world > 1 and not a.no_cpu_baseline and ncpu >= 2 * world + 2:
+    if a.full and world > 1 and not a.no_cpu_baseline and ncpu >= 2 * world + 2:
         try:
             mem_gb = os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES") / 2 ** 30
         except (ValueError, OSError):
             mem_gb = 64.0
         nref = max(1, min(world, int(mem_gb // 32)))
         if rank < nref:
-            cpu_n = CpuReference(payload, min(a.cpu_baseline_bytes, a.payload_bytes), (ncpu - 1 - rank,), modes=("-c",))
+            cpu_n = CpuReference(payload, min(a.cpu_baseline_bytes, payload_bytes), (ncpu - 1 - rank,), modes=("-c",))
             if not cpu_n.start():
                 cpu_n = None
         try:
             os.sched_setaffinity(0, set(range(ncpu - world)))
         except (AttributeError, OSError):
             pass
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and ncpu >= 4:
-        cpu = CpuReference(payload, min(a.cpu_baseline_bytes, a.payload_bytes), (ncpu - 1, ncpu - 2))
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and ncpu >= 4:
+        cpu = CpuReference(payload, min(a.cpu_baseline_bytes, payload_bytes), (ncpu - 1, ncpu - 2))
         cpu.serial = a.cpu_baseline_serial
         if a.cpu_baseline_serial:
             if not os.path.exists(cpu.exe):
@@ -294,11 +330,10 @@ def main():
     stream = text_file_stream(payload)
     t_framing = time.perf_counter() - t_c0
     n = len(stream)
-    # a step = 1/K of the stream's sub-chunks (whole sub-chunks: a ragged step would put a few-byte chunk into the pipeline)
-    nsub_total = -(-n // a.sub_chunk)
-    edges = [min(n, (i * nsub_total // a.steps) * a.sub_chunk) for i in range(a.steps)] + [n]
+    # a step = --step-bytes of the stream, whole sub-chunks (a ragged step would put a few-byte chunk into the pipeline); the last also carries the framing
+    step_bytes = a.step_bytes
+    edges = [i * step_bytes for i in range(a.steps)] + [n]
     step_sizes = [edges[i + 1] - edges[i] for i in range(a.steps)]
-    step_bytes = max(step_sizes)
 
     # ---- warm-up: the same code on a throw-away engine over the head of the shard ----
     wn = 0
@@ -337,6 +372,8 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     total_bytes, dt, _ = shard.aggregate_throughput(n, dt, None)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"compressed": np.frombuffer(blob, np.uint8), "p_last_step": eng.p_dev[8 * edges[-2]:8 * n].cpu().numpy()})
     host = eng.pipe.host_ms()
     st = eng.pipe.stage_totals()
     nsub = max(st["chunks"], 1)
@@ -351,11 +388,11 @@ def main():
     mode_name = "tolerance" if eng.pipe.mixnet_mode() == 1 else "strict"
     # ---- every rank verifies its own shard (N > 1): the first 128 KB on a fresh engine against the reference binary's file for ITS seed ----
     rank_checks = None
-    if world > 1:
+    if a.full and world > 1:
         mine = {"rank": rank, "seed": shard.shard_seed(rank), "fixture": None, "identical_to_reference_file": None}
         # (rank 0's WHOLE file is compared below; its entry is filled from that)
         fxr = os.path.join(ROOT, "tests", "golden", "dropin_rich_128k_s%d.npz" % shard.shard_seed(rank))
-        if rank and os.path.exists(fxr) and a.payload_bytes >= 131072 and mode_name == "strict":
+        if rank and os.path.exists(fxr) and payload_bytes >= 131072 and mode_name == "strict":
             with np.load(fxr) as z:
                 w_sha, w_size = z["sha256"].tobytes().hex(), int(z["size"][0])
             eng.close()
@@ -367,7 +404,7 @@ def main():
         rank_checks = [None] * world
         dist.all_gather_object(rank_checks, mine)
     cpu_all = None
-    if world > 1:
+    if a.full and world > 1:
         mine_cpu = None
         if cpu_n is not None:
             r = cpu_n.result()
@@ -378,12 +415,12 @@ def main():
         sha = hashlib.sha256(blob).hexdigest()
         verified = {"output_bytes": len(blob), "sha256": sha, "fixture": None, "identical_to_reference_file": None,
                     "full_shard_parity": FULL_SHARD_PARITY}
-        name = "dropin_1m.npz" if a.payload_bytes == 1 << 20 else "dropin_rich_%dk.npz" % (a.payload_bytes >> 10)
+        name = "dropin_1m.npz" if payload_bytes == 1 << 20 else "dropin_rich_%dk.npz" % (payload_bytes >> 10)
         fx = os.path.join(ROOT, "tests", "golden", name)
         if os.path.exists(fx):
             with np.load(fx) as z:
                 want_sha, want_size, seed, fx_rich = z["sha256"].tobytes().hex(), int(z["size"][0]), z["seed"], "rich" in z.files
-            if int(seed[0]) == a.payload_bytes and int(seed[1]) == shard.shard_seed(0) and fx_rich:
+            if int(seed[0]) == payload_bytes and int(seed[1]) == shard.shard_seed(0) and fx_rich:
                 verified.update(fixture="tests/golden/" + name, reference_bytes=want_size, identical_to_reference_file=bool(sha == want_sha and len(blob) == want_size))
         period_stage = max(us, key=us.get)
         V = int(eng.vocab.sum())
@@ -404,15 +441,15 @@ def main():
                 "workload": "enwik8-shaped shard (cmix_amd.synth.enwik_like, seed 1000 + rank, rich alphabet), first %d bytes, compressed as `cmix -c` does: "
                             "TEXT-block stream through the FULL model ensemble (2078 layer-0 inputs: contexts + 54 small models, PPMd host stage, "
                             "LSTM, fxcm 431, paq8 1591 -- every column produced by an engine stage, no stand-ins) + final mixing network + SSE, "
-                            "strict bit-exact mode, + arithmetic coder; output file checked against the reference binary's" % a.payload_bytes,
-                "payload_bytes": a.payload_bytes, "stream_bytes": n, "sub_chunk_bytes": a.sub_chunk, "vocab": V, "warmup_stream_bytes": wn,
+                            "strict bit-exact mode, + arithmetic coder; output file checked against the reference binary's" % payload_bytes,
+                "payload_bytes": payload_bytes, "stream_bytes": n, "sub_chunk_bytes": a.sub_chunk, "vocab": V, "warmup_stream_bytes": wn,
                 "parallelism": "1 stream per GPU, no collective",
                 "cpu_baseline_rule": "the reference binary is timed on the first %d bytes of the same payload (a bounded prefix: the whole payload would cost it ~%d minutes), "
-                                     "minus a 256-byte run; it slows down by ~10 %% between 128 KB and 1 MiB, so the prefix figure favours the reference" % (min(a.cpu_baseline_bytes, a.payload_bytes), a.payload_bytes // 320 // 60),
+                                     "minus a 256-byte run; it slows down by ~10 %% between 128 KB and 1 MiB, so the prefix figure favours the reference" % (min(a.cpu_baseline_bytes, payload_bytes), payload_bytes // 320 // 60),
                 "mode": ("tolerance (--tolerance -> cmx_pipeline_set_tolerance: tree-sum dot products in the final mixing network; NOT bit-exact, the output is not the "
                          "reference's file and `verified` says so)") if mode_name == "tolerance" else "strict (bit-exact; the default and the only mode that claims stream parity)"},
             "us_per_bit": dt / (8.0 * n) * 1e6,
-            "end_to_end": {"value": a.payload_bytes * world / (dt + t_construct), "unit": "input bytes/s", "construct_s": t_construct, "construct_first_s": t_framing + t_cold, "construct_warm_s": t_framing + t_warm,
+            "end_to_end": {"value": payload_bytes * world / (dt + t_construct), "unit": "input bytes/s", "construct_s": t_construct, "construct_first_s": t_framing + t_cold, "construct_warm_s": t_framing + t_warm,
                            "note": "payload bytes / (framing + engine construction: ~20 GB of tables allocated and initialised; the SLOWER of the process's first construction -- the warm-up engine's, "
                                    "HIP context included: construct_first_s -- and the timed engine's own, construct_warm_s -- + the timed run incl. the coder); "
                                    "`value` above is the predictor-only figure of SURVEY.md 8d (stream bytes / the Compress() loop)"},
@@ -448,11 +485,11 @@ def main():
                 out["cpu_baseline"] = {"value": sum(c["value"] for c in good), "unit": "input bytes/s", "cores": len(good), "kind": "reference", "cpu_model": good[0]["cpu_model"],
                                        "host_cores": ncpu, "concurrent_with_gpu_run": True, "per_rank": [{k: c[k] for k in ("rank", "value", "core")} for c in good],
                                        "sample": "%d concurrent pinned processes of oracle/_ref/cmix_O3 -c, one per rank on the first %d bytes of that rank's shard (minus a 256-byte run: "
-                                                 "construction), beside the timed GPU run; value = the sum of their bytes/s; rank 0's: %s" % (len(good), min(a.cpu_baseline_bytes, a.payload_bytes), good[0]["sample"])}
+                                                 "construction), beside the timed GPU run; value = the sum of their bytes/s; rank 0's: %s" % (len(good), min(a.cpu_baseline_bytes, payload_bytes), good[0]["sample"])}
                 out["speedup_vs_cpu_reference"] = out["value"] / out["cpu_baseline"]["value"]
             else:
                 out["cpu_baseline"] = {"error": "no rank's reference run finished: %s" % [c.get("error") if c else None for c in cpu_all]}
-        if world == 1 and a.decode_bytes > 0 and mode_name == "strict":
+        if a.full and world == 1 and a.decode_bytes > 0 and mode_name == "strict":
             eng.close()
             out["decode"] = decode_leg(payload, a.decode_bytes, local)
         if cpu is not None:

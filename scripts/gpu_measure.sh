@@ -14,21 +14,21 @@ if [ "$CMX_SKIP_TESTS" != "1" ]; then
 cp gpurun_out/decode_time.txt gpurun_out/config3_dict_time.txt gpurun_out/config4_silesia_time.txt $O/ 2>/dev/null
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $O/smoke.txt
 fi
-timeout 600 python bench.py > $O/bench_1m.json 2> $O/bench_1m.err; cut -c1-400 $O/bench_1m.json; tail -2 $O/bench_1m.err
-( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o pipe -- python $R/bench.py --payload-bytes 262144 --steps 8 --warmup 1 --no-cpu-baseline --decode-bytes 0 > $R/$O/prof_bench_256k.json 2> $R/$O/prof.err )
+timeout 600 python bench.py --full > $O/bench_1m.json 2> $O/bench_1m.err; cut -c1-400 $O/bench_1m.json; tail -2 $O/bench_1m.err
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o pipe -- python $R/bench.py --steps 8 --step-bytes 32768 --warmup 1 > $R/$O/prof_bench_256k.json 2> $R/$O/prof.err )
 for f in $(find $O/prof -name '*kernel_stats*.csv'); do grep -v "at::native\|rocclr" $f | head -30 > $O/bench_256k_kernel_stats.csv; done
 cut -c1-160 $O/bench_256k_kernel_stats.csv | head -12
 # A/B of opt-in kernel variants in the pipeline (256 KB, no CPU baseline): CMX_AB="CMX_MIXNET_SEG8=1 ..." (one variable assignment per variant)
 for v in $CMX_AB; do
-  ( export "$v"; timeout 200 python bench.py --payload-bytes 262144 --steps 5 --warmup 1 --no-cpu-baseline > "$O/bench_256k_$v.json" 2> "$O/bench_256k_$v.err" )
+  ( export "$v"; timeout 200 python bench.py --steps 4 --step-bytes 65536 --warmup 1 > "$O/bench_256k_$v.json" 2> "$O/bench_256k_$v.err" )
   python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['stage_us_per_bit'])" "$O/bench_256k_$v.json" "$v" 2>&1 | cut -c1-300
 done
 if [ "$CMX_SKIP_PMC" != "1" ]; then
 for c in FETCH_SIZE WRITE_SIZE; do
-( cd /tmp && timeout -k 5 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$O/pmc -o pmc_$c -- python $R/bench.py --payload-bytes 131072 --steps 4 --warmup 1 --no-cpu-baseline --decode-bytes 0 > $R/$O/pmc_$c.out 2> $R/$O/pmc_$c.err ; echo "rocprofv3 $c rc=$?" )
+( cd /tmp && timeout -k 5 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$O/pmc -o pmc_$c -- python $R/bench.py --steps 4 --step-bytes 32768 --warmup 1 > $R/$O/pmc_$c.out 2> $R/$O/pmc_$c.err ; echo "rocprofv3 $c rc=$?" )
 done
 # one occupancy pass (round-5 review 4 iv): waves launched, cycles the SQ was busy, cycles waves waited for any instruction, per kernel
-( cd /tmp && timeout -k 5 300 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $R/$O/pmc -o pmc_SQ -- python $R/bench.py --payload-bytes 131072 --steps 4 --warmup 1 --no-cpu-baseline --decode-bytes 0 > $R/$O/pmc_SQ.out 2> $R/$O/pmc_SQ.err ; echo "rocprofv3 SQ rc=$?" )
+( cd /tmp && timeout -k 5 300 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $R/$O/pmc -o pmc_SQ -- python $R/bench.py --steps 4 --step-bytes 32768 --warmup 1 > $R/$O/pmc_SQ.out 2> $R/$O/pmc_SQ.err ; echo "rocprofv3 SQ rc=$?" )
 python - "$O" <<'PY'
 import csv, glob, collections, json, sys
 O = sys.argv[1]
@@ -44,7 +44,7 @@ for f in sorted(set(glob.glob(O + '/pmc/**/*counter_collection*.csv', recursive=
                 out.setdefault(k, {})[c] = {"sum": v, "launches": n[(k, c)]}
 # bytes of stream the profiled command pushed through the stages: the timed stream + the warm-up engine's, as the bench line of that run reports them
 b = json.load(open(O + '/pmc_FETCH_SIZE.out'))
-out["_meta"] = {"stream_bytes_processed": b["config"]["stream_bytes"] + b["config"]["warmup_stream_bytes"], "command": "python bench.py --payload-bytes 131072 --steps 4 --warmup 1 --no-cpu-baseline",
+out["_meta"] = {"stream_bytes_processed": b["config"]["stream_bytes"] + b["config"]["warmup_stream_bytes"], "command": "python bench.py --steps 4 --step-bytes 32768 --warmup 1",
                 "unit": "KB summed over the launches (rocprofv3 FETCH_SIZE / WRITE_SIZE); bench.py uses 2 x FETCH_SIZE + WRITE_SIZE"}
 json.dump(out, open(O + '/pmc_bench.json', 'w'), indent=1)
 for k, v in out.items():

@@ -8,6 +8,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
+# Each stage of a stream runs on a HIP stream of its own, and the decoder's form of the engine needs all 14 of them running at once
+# (include/cmix_amd.h, section 3). libcmixamd asks for 16 hardware queues only where GPU_MAX_HW_QUEUES is unset, so a smaller value
+# from the environment is raised here, before HIP starts: for this process and for the processes the tests start.
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "16"))
+except ValueError:
+    _queues = 0
+if _queues < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
+
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 GOLDEN_BIG = os.path.join(ROOT, "oracle", "_ref", "golden")
 

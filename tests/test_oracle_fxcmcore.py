@@ -2,12 +2,14 @@
 reference's own structs compiled from fxcmv1.cpp (oracle/ref_fxcmcore.cpp -> oracle/_ref/libcmixreffxcm.so). Integer
 work: bit-exact."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
 from oracle import refharness as R
+from conftest import ROOT
 
 
 @pytest.fixture(autouse=True)
@@ -384,7 +386,7 @@ def test_whole_fxcm_model_vs_reference_across_block_position_thresholds(blpos, t
             assert bad.size == 0 and pr == pg, (blpos, n, bpos, bad[:8], pr, pg)
 
 
-DICTIONARY = "/root/reference/dictionary/english.dic"
+DICTIONARY = os.path.join(ROOT, "oracle", "_ref", "english.dic")   # the reference's dictionary, copied by `make -C oracle ref`
 
 
 def _wrt_codewords():
@@ -408,7 +410,7 @@ def _wrt_codewords():
 
 
 @needs_ref
-@pytest.mark.skipif(not __import__("os").path.exists(DICTIONARY), reason="the reference's dictionary is not on this box")
+@pytest.mark.skipif(not os.path.exists(DICTIONARY), reason="oracle/_ref/english.dic not built (make -C oracle ref)")
 def test_whole_fxcm_model_with_wrt_dictionary_vs_reference(tmp_path):
     """cmix -c <dictionary>: the stream carries WRT codewords (bytes 128..255) that fxcm decodes through the
     dictionary; the decoded words feed the stemmer and the <text> / <math> / <pre> / <nowiki> / </page> detectors, the
