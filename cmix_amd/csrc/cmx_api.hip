@@ -21,8 +21,6 @@
 
 extern "C" __global__ void cmx_mixnet_kernel(MixState*, const float*, const uint32_t*,
                                              const uint8_t*, const float*, int, float*, float*, int);
-extern "C" __global__ void cmx_mixnet_chunk_kernel(MixState*, const float*, const uint32_t*,
-                                                   const uint8_t*, const float*, int, float*, float*, int);
 extern "C" __global__ void cmx_mixnet_spec_kernel(MixState*, SpecXfer*, const float*, const uint32_t*, const uint8_t*, const float*, int, float*,
                                                   float*, int);
 extern "C" __global__ void cmx_mixnet_spec_jitter_kernel(MixState*, SpecXfer*, const float*, const uint32_t*, const uint8_t*, const float*, int, float*, float*, int);
@@ -135,9 +133,7 @@ struct cmx_mixnet {
   int rotate = 0;       // CMX_MIXNET_ROTATE=1 (test hook): the roles' workgroups move to another XCD with every launch (see spec_kernel_body)
   int jitter = 0;       // CMX_MIXNET_JITTER=1..15 (test hook, tests/test_gpu_mixnet.py): pseudo-random stalls in every role but the gather wave -- same results, every lead / lag between the roles
   int xcd = -1;         // CMX_MIXNET_XCD=k: place the persistent kernel on XCD k (speed only; -1 = wherever block 0 lands)
-  bool use_v1 = false;  // CMX_MIXNET_V1=1: run chunks through the bit-synchronous kernel
-  bool tolerance = false;   // cmx_mixnet_set_tolerance (opt-in through the API, NOT bit-exact): layer-0 dot products as f64 tree sums rounded once (cmx_mixnet_spec_kernel only)
-  bool use_spec = true; // cmx_mixnet_spec_kernel (26 helper workgroups, speculative segment-parallel chains); CMX_MIXNET_SPEC=0: the one-workgroup kernel
+  bool tolerance = false;   // cmx_mixnet_set_tolerance (opt-in through the API, NOT bit-exact): layer-0 dot products as f64 tree sums rounded once
   SpecXfer* d_xfer = nullptr;
   float* d_late_p = nullptr; size_t late_p_cap = 0;   // the decoder's form: the kernel's p[] array (the host reads p from the box)
   float* late_mix_cur[3] = {nullptr, nullptr, nullptr};
@@ -300,14 +296,6 @@ cmx_mixnet_t* cmx_mixnet_create(int device) {
     cmx_mixnet_destroy(h);
     return nullptr;
   }
-  if (hipFuncSetAttribute((const void*)cmx_mixnet_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          CMX_CHUNK_LDS_BYTES) != hipSuccess) {
-    set_err("hipFuncSetAttribute(MaxDynamicSharedMemorySize, chunk kernel) failed");
-    cmx_mixnet_destroy(h);
-    return nullptr;
-  }
-  { const char* v = getenv("CMX_MIXNET_V1"); h->use_v1 = v && v[0] == '1'; }
-  { const char* v = getenv("CMX_MIXNET_SPEC"); h->use_spec = !(v && v[0] == '0'); }
   h->d_xfer = (SpecXfer*)dalloc(sizeof(SpecXfer), true);   // incl. the zero padding of the input ring
   bool attr_ok = true;
   for (const void* k : {(const void*)cmx_mixnet_spec_kernel, (const void*)cmx_mixnet_spec_jitter_kernel, (const void*)cmx_mixnet_spec_late_kernel})
@@ -403,7 +391,6 @@ int cmx_cumask_on(void) { return cumask_wanted() && g_cumask_applied; }   // the
 // but cannot be decoded by the reference or by this library's decoder (which is strict), so no file-writing program sets it.
 int cmx_mixnet_set_tolerance(cmx_mixnet_t* h, int on) {
   if (!h) { set_err("cmx_mixnet_set_tolerance: null handle"); return 1; }
-  if (on && (!h->use_spec || h->use_v1)) { set_err("cmx_mixnet_set_tolerance: only the 27-workgroup kernel has the mode (CMX_MIXNET_SPEC=0 / CMX_MIXNET_V1 are set)"); return 1; }
   if (h->runs || h->bits_done) { set_err("cmx_mixnet_set_tolerance: only before the first bit of the stream"); return 1; }
   h->tolerance = on != 0;
   return 0;
@@ -442,10 +429,10 @@ int cmx_mixnet_run(cmx_mixnet_t* h, const float* d_probs, const uint32_t* d_sel,
   return mixnet_run_impl(h, d_probs, d_sel, d_bits, nbits, d_p_out, d_mix_out, stream, nullptr);
 }
 // The decoder's form of a chunk (cmx_late.h): rows and selectors (memory the producing kernels and this one see coherently) are
-// consumed as their stages count them in `box`; p(t) goes to the box, bit t comes back through it. Only the 27-workgroup kernel.
+// consumed as their stages count them in `box`; p(t) goes to the box, bit t comes back through it. Strict mode only.
 int cmx_mixnet_run_late(cmx_mixnet_t* h, void* box, const float* probs, const uint32_t* sel, size_t nbits, void* stream) {
   if (!h || !box) { set_err("cmx_mixnet_run_late: bad argument"); return 1; }
-  if (!h->use_spec || h->use_v1 || h->tolerance) { set_err("cmx_mixnet_run_late: a decoder needs the strict 27-workgroup kernel (CMX_MIXNET_SPEC=0, CMX_MIXNET_V1 or the tolerance switch is set)"); return 1; }
+  if (h->tolerance) { set_err("cmx_mixnet_run_late: a decoder needs the strict kernel (the tolerance switch is set)"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { set_err("hipSetDevice failed"); return 1; }
   if (h->late_p_cap < nbits || h->decay_cap < nbits) { set_err("cmx_mixnet_run_late: call cmx_mixnet_late_prepare first (nothing may be allocated while the stream's kernels run)"); return 1; }
   // (debug: three chunk-sized areas of mixer outputs in rotation, like the pipeline's buffer sets)
@@ -501,31 +488,21 @@ static int mixnet_run_impl(cmx_mixnet_t* h, const float* d_probs, const uint32_t
   HIP_OK(hipStreamWaitEvent(st, h->ev_decay[slot], 0));
   h->decay_used[slot] = true;
   HIP_OK(hipEventRecord(h->ev0, st));
-  if (h->use_v1)
-    hipLaunchKernelGGL(cmx_mixnet_kernel, dim3(1), dim3(CMX_MIXNET_THREADS), kLdsBytes, st, h->d_state,
-                       d_probs, d_sel, d_bits, dd, (int)nbits, d_p_out, d_mix_out,
-                       3 | (h->profile ? 4 : 0));
-  else if (h->use_spec) {
-    // epochs and value|tag words restart at 0 with every launch; 1 main + 26 helper workgroups, co-resident (27 of 256 CUs)
-    HIP_OK(hipMemsetAsync(h->d_xfer, 0, CMX_SPEC_HEADER_BYTES, st));
-    const bool cumask = cmx_cumask_on() != 0;   // the stream's compute-unit mask does the placement: 27 workgroups, all of them work, the XCC census still decides the hand-off's form
-    const int rot = h->rotate && h->xcd < 0 ? (int)((h->runs * 3) & 7) : 0;   // (h->runs was advanced above: the launch's number + 1; x 3: not the neighbouring XCD every time)
-    const int kmode = 3 | (rot << 8) | (h->profile ? 4 : 0) | ((h->dbg & 15) << 4) | (h->tolerance ? 0x1000 : 0) | (h->xcd >= 0 ? 0x20000 | ((h->xcd & 7) << 20) : 0) |
-                      (getenv("CMX_MIXNET_XCD_NOLOCAL") ? 0x800000 : 0) | (cumask ? 0x1000000 : 0) | (h->jitter ? 0x2000000 | ((h->jitter & 15) << 26) : 0);
-    static const bool padgrid = getenv("CMX_MIXNET_PADGRID") != nullptr;   // diagnostic: the 8 x 27 grid of the one-XCD placement without the placement (blocks 27.. leave at once)
-    const unsigned grid = (1 + CMX_SPEC_HELPERS) * ((h->xcd >= 0 && !cumask) || padgrid ? 8 : 1) + (unsigned)rot;   // placement: 8 x 27 workgroups, those with blockIdx % 8 == xcd work
-    if (box && box->box)   // a decoder's chunk: the patient instantiation of the same roles
-      hipLaunchKernelGGL(cmx_mixnet_spec_late_kernel, dim3(grid), dim3(CMX_SPEC_THREADS), CMX_SPEC_LDS_BYTES, st,
-                         h->d_state, h->d_xfer, d_probs, d_sel, dd, (int)nbits, d_p_out, d_mix_out, kmode, *box);
-    else {
-      hipLaunchKernelGGL(h->jitter ? cmx_mixnet_spec_jitter_kernel : cmx_mixnet_spec_kernel, dim3(grid), dim3(CMX_SPEC_THREADS), CMX_SPEC_LDS_BYTES, st,
-                         h->d_state, h->d_xfer, d_probs, d_sel, d_bits, dd, (int)nbits, d_p_out, d_mix_out, kmode);
-    }
-  } else
-    // XCD placement (observed: block b runs on XCD b % 8): 8 blocks, all but block `xcd` leave at once
-    hipLaunchKernelGGL(cmx_mixnet_chunk_kernel, dim3(h->xcd >= 0 ? 8 : 1), dim3(CMX_CHUNK_THREADS), CMX_CHUNK_LDS_BYTES, st,
-                       h->d_state, d_probs, d_sel, d_bits, dd, (int)nbits, d_p_out, d_mix_out,
-                       3 | (h->profile ? 4 : 0) | ((h->dbg & 15) << 4) | (h->xcd >= 0 ? ((h->xcd & 7) + 1) << 8 : 0));
+  // epochs and value|tag words restart at 0 with every launch; 1 main + 26 helper workgroups, co-resident (27 of 256 CUs)
+  HIP_OK(hipMemsetAsync(h->d_xfer, 0, CMX_SPEC_HEADER_BYTES, st));
+  const bool cumask = cmx_cumask_on() != 0;   // the stream's compute-unit mask does the placement: 27 workgroups, all of them work, the XCC census still decides the hand-off's form
+  const int rot = h->rotate && h->xcd < 0 ? (int)((h->runs * 3) & 7) : 0;   // (h->runs was advanced above: the launch's number + 1; x 3: not the neighbouring XCD every time)
+  const int kmode = 3 | (rot << 8) | (h->profile ? 4 : 0) | ((h->dbg & 15) << 4) | (h->tolerance ? 0x1000 : 0) | (h->xcd >= 0 ? 0x20000 | ((h->xcd & 7) << 20) : 0) |
+                    (getenv("CMX_MIXNET_XCD_NOLOCAL") ? 0x800000 : 0) | (cumask ? 0x1000000 : 0) | (h->jitter ? 0x2000000 | ((h->jitter & 15) << 26) : 0);
+  static const bool padgrid = getenv("CMX_MIXNET_PADGRID") != nullptr;   // diagnostic: the 8 x 27 grid of the one-XCD placement without the placement (blocks 27.. leave at once)
+  const unsigned grid = (1 + CMX_SPEC_HELPERS) * ((h->xcd >= 0 && !cumask) || padgrid ? 8 : 1) + (unsigned)rot;   // placement: 8 x 27 workgroups, those with blockIdx % 8 == xcd work
+  if (box && box->box)   // a decoder's chunk: the patient instantiation of the same roles
+    hipLaunchKernelGGL(cmx_mixnet_spec_late_kernel, dim3(grid), dim3(CMX_SPEC_THREADS), CMX_SPEC_LDS_BYTES, st,
+                       h->d_state, h->d_xfer, d_probs, d_sel, dd, (int)nbits, d_p_out, d_mix_out, kmode, *box);
+  else {
+    hipLaunchKernelGGL(h->jitter ? cmx_mixnet_spec_jitter_kernel : cmx_mixnet_spec_kernel, dim3(grid), dim3(CMX_SPEC_THREADS), CMX_SPEC_LDS_BYTES, st,
+                       h->d_state, h->d_xfer, d_probs, d_sel, d_bits, dd, (int)nbits, d_p_out, d_mix_out, kmode);
+  }
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(h->ev_kdone[slot], st));
   HIP_OK(hipEventRecord(h->ev1, st));

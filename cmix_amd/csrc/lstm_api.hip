@@ -32,7 +32,6 @@ extern "C" __global__ void cmx_bytemodel_bits(const float*, const float*, const 
                                               float*);
 extern "C" __global__ void cmx_bytemodel_late_kernel(CmxLate, size_t, const float*, const float*, const float*, const float*, const float*, const uint32_t*, uint32_t,
                                                      const uint32_t*, uint32_t, float*, size_t, int16_t*, uint8_t*, uint8_t*, const cmx_late_relay_t*, int);
-extern "C" __global__ void cmx_late_bump_kernel(uint32_t*, uint32_t, uint32_t*, uint32_t);
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
 
@@ -89,7 +88,6 @@ cmx_lstm_t* cmx_lstm_create(const uint8_t vocab[256], int skip_rand, int device)
   S.rowlen[1] = S.insz[1] + V;
   S.lr = 0.03f;
   { const char* v = getenv("CMX_LSTM_XCD"); S.xcd = v ? atoi(v) : -1; }
-  { const char* v = getenv("CMX_LSTM_SLEEP"); S.poll_sleep = v && v[0] == '1'; }
   { const char* v = getenv("CMX_LSTM_AVOID_XCD"); if (!v) v = getenv("CMX_MIXNET_XCD"); S.avoid_xcd = v ? atoi(v) : CMX_MIXNET_XCD_DEFAULT; if (S.avoid_xcd > 7) S.avoid_xcd = -1; }   // the mixing network's XCD (mixnet_state.h)
   bool fail = false;
   auto dallocf = [&](size_t count, const float* init) -> float* {
@@ -351,13 +349,6 @@ int cmx_bytemodel_late_run(int device, void* box, size_t nbytes, const float* br
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { cmx_set_err(std::string("cmx_bytemodel_late_run: ") + hipGetErrorString(e)); return 1; }
   return 0;
-}
-// one system-scope store behind everything already in `stream`: *counter = value (and *counter2 = value2 when given)
-int cmx_late_bump(int device, uint32_t* counter, uint32_t value, uint32_t* counter2, uint32_t value2, void* stream) {
-  if (!counter) { cmx_set_err("cmx_late_bump: bad argument"); return 1; }
-  if (hipSetDevice(device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
-  hipLaunchKernelGGL(cmx_late_bump_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counter, value, counter2, value2);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 // the distribution the LSTM byte mixer holds between bytes (DEVICE memory, [256]; uniform until the first byte)
 const float* cmx_lstm_byte_probs(cmx_lstm_t* h) { return h ? h->h_state.byte_probs : nullptr; }

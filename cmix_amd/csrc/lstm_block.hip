@@ -52,11 +52,10 @@ __device__ __forceinline__ void st_f(float* p, float v) { __hip_atomic_store(p, 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // lane 0 polls the counter, the workgroup waits at the barrier
-__device__ __forceinline__ void wg_wait(const unsigned* p, unsigned want, unsigned* fail, int sleepy) {
+__device__ __forceinline__ void wg_wait(const unsigned* p, unsigned want, unsigned* fail) {
   if (threadIdx.x == 0) {
     unsigned it = 0;
     while (ld_u(p) < want) {
-      if (sleepy) __builtin_amdgcn_s_sleep(1);   // A/B (CMX_LSTM_SLEEP): a poll every ~64 clocks instead of back to back
       if ((++it & 1023u) == 0 && (it > SPIN_LIMIT || ld_u(fail))) {
         __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         break;
@@ -68,8 +67,8 @@ __device__ __forceinline__ void wg_wait(const unsigned* p, unsigned want, unsign
 // The decoder's form of a forward block (cmx_lstm_fwdblk_late): the launch covers bytes that do not exist yet, so every in-launch wait may last as long as the
 // decoder (host) takes -- bounded by the box's abort / fail words and 30 s of wall-clock time (cmx_late.h), not by a spin count. A wait that ends that way sets
 // LstmSync::fail: every later wait of the launch then falls through and the kernel drains.
-template <bool LATE> __device__ __forceinline__ void wg_wait_t(const unsigned* p, unsigned want, unsigned* fail, int sleepy, CmxLateBox* B) {
-  if (!LATE) { wg_wait(p, want, fail, sleepy); return; }
+template <bool LATE> __device__ __forceinline__ void wg_wait_t(const unsigned* p, unsigned want, unsigned* fail, CmxLateBox* B) {
+  if (!LATE) { wg_wait(p, want, fail); return; }
   if (threadIdx.x == 0 && ld_u(p) < want) {
     unsigned it = 0;
     unsigned long long t0 = 0;
@@ -171,7 +170,7 @@ template <bool LATE> __device__ __forceinline__ void fb_finish_layer(const LstmS
                                                 float* xh, float& st, CmxLateBox* LB, const void* late_ptr = nullptr) {
   const int tid = threadIdx.x;
   LstmSync* Y = S->sync;
-  wg_wait_t<LATE>(&Y->raw_cnt[layer][e], GL, &Y->fail, S->poll_sleep, LB);
+  wg_wait_t<LATE>(&Y->raw_cnt[layer][e], GL, &Y->fail, LB);
   const float* rr = S->raw_ring + ((size_t)layer * H + e) * (3 * C);
   for (int idx = tid; idx < 3 * C; idx += FT) rawl[idx] = ld_f(rr + idx);
   lds_barrier();
@@ -289,7 +288,7 @@ template <bool LATE> __device__ void fb_gate_wg(const LstmState* S, const FbArgs
     if (lead && tid < C) li[V + tid] = xv[V + tid];   // keep the assembled vector for BPTT
     if (tid < 64) f = lds_chain(f, Wl, R, r, xv, V, V + C);
     if (layer == 1) {  // layer 0's new hidden (lstm.cpp:127-131)
-      wg_wait_t<LATE>(&Y->h_flag[0][e], 1, &Y->fail, S->poll_sleep, LB);
+      wg_wait_t<LATE>(&Y->h_flag[0][e], 1, &Y->fail, LB);
       if (tid < C) {
         const float h = ld_f(&S->h_ring[(size_t)e * NH + tid]);
         xv[V + C + tid] = h;
@@ -378,12 +377,12 @@ template <bool LATE> __device__ void fb_out_wg(const LstmState* S, const FbArgs&
       }
       OLs[(size_t)q * RP + rr] = v;
     }
-    wg_wait_t<LATE>(&Y->h_flag[0][e], 1, &Y->fail, S->poll_sleep, LB);
+    wg_wait_t<LATE>(&Y->h_flag[0][e], 1, &Y->fail, LB);
     if (tid < C) hcur[tid] = ld_f(&S->h_ring[(size_t)e * NH + tid]);
     lds_barrier();
     float sum = 0.0f;
     if (tid < 64) sum = lds_chain(sum, OLs, RP, r, hcur, 0, C);
-    wg_wait_t<LATE>(&Y->h_flag[1][e], 1, &Y->fail, S->poll_sleep, LB);
+    wg_wait_t<LATE>(&Y->h_flag[1][e], 1, &Y->fail, LB);
     if (tid < C) hcur[C + tid] = ld_f(&S->h_ring[(size_t)e * NH + C + tid]);
     if (tid == 0) hcur[2 * C] = 1.0f;   // bias element of hidden_ (lstm.cpp:18)
     lds_barrier();
@@ -392,7 +391,7 @@ template <bool LATE> __device__ void fb_out_wg(const LstmState* S, const FbArgs&
       if (tid < nr) st_f(&S->logit_ring[(size_t)e * VP + i0 + tid], sum);
       wave_signal(&Y->logit_cnt[e]);
     }
-    wg_wait_t<LATE>(&Y->logit_cnt[e], GO, &Y->fail, S->poll_sleep, LB);
+    wg_wait_t<LATE>(&Y->logit_cnt[e], GO, &Y->fail, LB);
     float lg = 0.0f;
     if (tid < V) lg = ld_f(&S->logit_ring[(size_t)e * VP + tid]);
     red[tid] = tid < V ? lg : 0.0f;   // max_out starts at 0 (lstm.cpp:132)
@@ -593,7 +592,7 @@ extern "C" __global__ __launch_bounds__(LSTM_BP_THREADS) void cmx_lstm_bpttblk(c
     lds_barrier();   // slice s+2 is in LDS
     // the next step's chain does not depend on this step when it starts from zero (layer 0 leaves hidden_error_ = 0)
     if (layer == 0 && s + 1 < 2 * H && tid < 64) hpre = p1_chain(s + 1, 0.0f);
-    wg_wait(&Y->bp_cnt[s], GB, &Y->fail, S->poll_sleep);
+    wg_wait(&Y->bp_cnt[s], GB, &Y->fail);
     if (tid < C) {
       const float h = ld_f(pub + (size_t)s * 2 * C + tid);
       if (s > 0) stored_o = ld_f(pub + (size_t)s * 2 * C + C + tid);   // the previous step's layer

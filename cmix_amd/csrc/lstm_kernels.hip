@@ -324,11 +324,3 @@ cmx_bytemodel_late_kernel(CmxLate B, size_t nbytes, const float* brk0, const flo
   }
   (void)T;
 }
-
-// one store behind whatever is in front of it in the stream: the late pipeline's "the LSTM distribution of byte n is there"
-extern "C" __global__ void cmx_late_bump_kernel(uint32_t* counter, uint32_t value, uint32_t* counter2, uint32_t value2) {
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(counter, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (counter2) __hip_atomic_store(counter2, value2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}

@@ -54,7 +54,6 @@ struct LstmState {
   unsigned char vocab[256];
   float lr;                      // 0.03
   int xcd;                       // >= 0: the single-workgroup kernels run as block `xcd` of 8 (XCD placement, speed only)
-  int poll_sleep;                // A/B switch (CMX_LSTM_SLEEP=1): s_sleep 1 between two polls of an in-launch counter
   int avoid_xcd;                 // >= 0: the block kernels leave this XCD to the mixing network (CMX_MIXNET_XCD: its 27 workgroups share that XCD's L2) --
                                  //   the grids are padded and the blocks with blockIdx % 8 == avoid_xcd exit (observed: block b runs on XCD b % 8; speed only)
 

@@ -96,8 +96,4 @@ struct SpecXfer {
 #define CMX_SPEC_HEADER_BYTES (64 + 128 + 2 * 32 * 8)   /* what the host clears ahead of every launch (epochs and tags restart at 0) */
 #define CMX_SPEC_LDS_BYTES 147456  /* main workgroup: 128 KB of SSE tables + records; a helper uses 9 KB of it */
 
-// dynamic LDS of cmx_mixnet_chunk_kernel (see the carve-up in mixnet_chunk.hip)
-#define CMX_CHUNK_LDS_BYTES 163840   /* the whole 160 KB LDS of a gfx950 CU: one workgroup per CU */
-#define CMX_CHUNK_THREADS 768
-
 #endif

@@ -164,7 +164,6 @@ struct Late {
   uint32_t timeout_s = 0;  // CMX_LATE_TIMEOUT_S: seconds an in-launch wait of a decoder's kernels may last without progress (0: the 30 s default)
   bool push = false;       // the decoder thread stores steps into device memory itself (large BAR; CMX_LATE_PULL=1: rounds 4 / 5's relay wave instead)
   int lstm_covered = 0;    // bytes of the chunk in progress that the LSTM's last forward launch still covers (cmx_lstm_run_late)
-  bool lstm_per_byte = false;   // CMX_LATE_LSTM_PER_BYTE=1: rounds 4 / 5's one launch per byte (A/B)
   float* dbg_row = nullptr; uint32_t* dbg_sel = nullptr;   // pinned: cmx_pipeline_late_debug_row
   uint64_t mix_chunk0 = 0;                                  // the mixing-network handle's launch count when the stream started (debug hook)
 };
@@ -233,7 +232,7 @@ __global__ void cmx_fxcm_hints_kernel(const float* layer0, long stride, const fl
 extern "C" {
 
 // Co-residency: the stage kernels of a stream run for a whole chunk and hand values to each other inside the launch (bounded waits), so
-// all of their workgroups must be resident at once -- mixing network 27 (1 with CMX_MIXNET_SPEC=0), LSTM 52, contexts 1, fxcm 4, paq8 10 --
+// all of their workgroups must be resident at once -- mixing network 27, LSTM 52, contexts 1, fxcm 4, paq8 10 --
 // and most of them own a compute unit (130-160 KB of LDS). An engine that would take the device past its compute-unit count is refused at
 // construction (with the reason) instead of timing out in the middle of a stream. Process-wide per device.
 static std::mutex g_wg_mu;
@@ -245,7 +244,7 @@ static bool wg_claim(cmx_pipeline* h, int n, const char* what) {
   int& used = g_wg_used[h->device & 63];
   if (used + n > cus) {
     cmx_set_err(std::string(what) + ": " + std::to_string(used) + " workgroups of persistent stage kernels are already resident on device " + std::to_string(h->device) + " and this stage needs " +
-                std::to_string(n) + " more, the device has " + std::to_string(cus) + " compute units (fewer streams per GPU, or CMX_MIXNET_SPEC=0 for the one-workgroup mixing network)");
+                std::to_string(n) + " more, the device has " + std::to_string(cus) + " compute units (fewer streams per GPU)");
     return false;
   }
   used += n; h->wgs += n;
@@ -318,10 +317,7 @@ cmx_pipeline_t* cmx_pipeline_create(const uint8_t vocab[256], int device, size_t
   cmx_pipeline_t* h = new cmx_pipeline();
   h->device = device;
   h->max_chunk = max_chunk_bytes;
-  {
-    const char* sp = getenv("CMX_MIXNET_SPEC");
-    if (cmx_device_count() > 0 && !wg_claim(h, ((sp && sp[0] == '0') ? 1 : 27) + 52 + 1, "cmx_pipeline_create")) { delete h; return nullptr; }
-  }
+  if (cmx_device_count() > 0 && !wg_claim(h, 27 + 52 + 1, "cmx_pipeline_create")) { delete h; return nullptr; }   // mixing network, LSTM, contexts
   // every stage reports its own failure (no device, out of memory) through cmx_last_error()
   h->ctx = cmx_ctxmodels_create(vocab, device);
   h->lstm = h->ctx ? cmx_lstm_create(vocab, 31, device) : nullptr;  // 31 rand() draws precede the LSTM (indirect.cpp:10)
@@ -445,7 +441,7 @@ int cmx_pipeline_enable_paq8(cmx_pipeline_t* h) {
 int cmx_pipeline_set_tolerance(cmx_pipeline_t* h, int on) {
   if (!h) { cmx_set_err("cmx_pipeline_set_tolerance: null handle"); return 1; }
   if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_tolerance: only before the first chunk"); return 1; }
-  // the mixing network first (it can refuse: CMX_MIXNET_SPEC=0 / CMX_MIXNET_V1 have no tolerance form); the LSTM's switch (its weight-update contraction
+  // the mixing network first (it can refuse: after the stream's first bit); the LSTM's switch (its weight-update contraction
   // on the matrix cores) follows and is rolled back with the network's if it fails, so that the two never disagree about the mode
   const int was = cmx_mixnet_mode(h->mix);
   if (cmx_mixnet_set_tolerance(h->mix, on)) return 1;
@@ -886,7 +882,6 @@ int cmx_pipeline_late_start(cmx_pipeline_t* h, int last_bit) {
   }
   if (hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_pipeline_late_start: device error"); L->failed = true; return 1; }
   L->lstm0 = cmx_lstm_byte_probs(h->lstm);
-  { const char* v = getenv("CMX_LATE_LSTM_PER_BYTE"); L->lstm_per_byte = v && v[0] == '1'; }
   { const char* v = getenv("CMX_LATE_TIMEOUT_S"); const long t = v ? atol(v) : 0; L->timeout_s = t > 0 ? (uint32_t)(t < 86400 ? t : 86400) : 0u; }   // (the host's own bound in late_predict follows: twice this, at least 60 s)
   {   // host push needs the device's memory in this process's address space (large BAR); CMX_LATE_PULL=1 keeps the relay wave (A/B, and the fall-back)
     int bar = 0;
@@ -1022,10 +1017,7 @@ int cmx_pipeline_late_perceive(cmx_pipeline_t* h, int bit) {
   }
   // ---- the LSTM byte mixer's step for the completed byte (predictor.cpp:450-461), then "its distribution is there" ----
   if (byte_done) {
-    if (L->lstm_per_byte) {
-      if (cmx_lstm_run(h->lstm, q.ppmd + (b + 1) * 256, q.bytes + b, 1, q.lstm + b * 256, nullptr, 0, nullptr, h->s_lstm)) return 1;
-      if (cmx_late_bump(h->device, q.cnt + LC_LSTM * CMX_LATE_CNT_STRIDE, q.lt.base | (uint32_t)(b + 1), nullptr, 0, h->s_lstm)) { cmx_set_err("cmx_pipeline_late_perceive: launch failed"); return 1; }
-    } else if (L->lstm_covered == 0) {   // a new truncated-BPTT block or a new chunk begins with this byte: one launch for all of its bytes, which wait for theirs inside it
+    if (L->lstm_covered == 0) {   // a new truncated-BPTT block or a new chunk begins with this byte: one launch for all of its bytes, which wait for theirs inside it
       const int c = cmx_lstm_run_late(h->lstm, &q.lt, q.d_ppmd, q.ppmd, q.bytes, q.lstm, b, n, h->s_lstm);
       if (c < 1) return 1;
       L->lstm_covered = c - 1;

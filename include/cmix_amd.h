@@ -343,7 +343,6 @@ int cmx_ppmd_run(cmx_ppmd_t*, const uint8_t* bytes, size_t nbytes, float* out_pr
  *                          onto 4 hardware queues by default. The library sets 16 when it is loaded unless the variable is set.
  *   CMX_PIPELINE_STREAMS   2 or 1: throughput mode for several streams per GPU -- fewer hardware queues per engine (8 or 6;
  *                          roles take turns on shared streams, the per-stream period grows)
- *   CMX_MIXNET_SPEC=0      the one-workgroup mixing-network kernel (1 compute unit per stream instead of 27: many streams per GPU)
  *   CMX_MIXNET_XCD=k       the mixing network's 27 workgroups on XCD k, hand-off words through that XCD's L2 (bit-exact either way)
  *   CMX_MIXNET_JITTER=1..15  test hook: pseudo-random stalls in the mixing network's roles (bit-exact by construction; tests/test_gpu_mixnet.py)
  *   (tolerance mode is NOT an environment switch: cmx_mixnet_set_tolerance / cmx_lstm_set_tolerance / cmx_pipeline_set_tolerance --
@@ -351,7 +350,7 @@ int cmx_ppmd_run(cmx_ppmd_t*, const uint8_t* bytes, size_t nbytes, float* out_pr
  *   CMX_P8CM_SERIAL        1: paq8's table families walk every instance serially (A/B timing); 2: the ContextMap family's narrowed walk takes
  *                          its whole-instance fall-back at every second visit (test switch)
  * Co-residency: a stream's stage kernels run for a whole chunk and wait for each other inside the launch, so their workgroups -- 94 per
- * stream (68 with CMX_MIXNET_SPEC=0), most of them a compute unit each -- must all be resident. cmx_pipeline_create / _enable_fxcm /
+ * stream, most of them a compute unit each -- must all be resident. cmx_pipeline_create / _enable_fxcm /
  * _enable_paq8 keep count per device and refuse (cmx_last_error says why) an engine that would exceed the device's compute units.
  *   CMX_FXCM_PROFILE, CMX_P8FAM_PROFILE, CMX_MIXNET_DBG     in-kernel phase timers / timing experiments (scripts/gpu_*prof*) */
 #define CMX_PIPELINE_SLOTS 8   /* chunks in flight per stream (layer-0 matrices the caller cycles through) */
@@ -491,7 +490,6 @@ void* cmx_late_alloc_dev(int device, size_t bytes);   /* zeroed UNCACHED device 
 void cmx_late_free_dev(void* p);
 size_t cmx_late_box_bytes(size_t nbits);   /* allocation size of a box for a chunk of nbits */
 /* `box` of the per-stage entry points below: a `const CmxLate*` (cmx_late.h) = the host box, the chunk's row counters and their base */
-int cmx_late_bump(int device, uint32_t* counter, uint32_t value, uint32_t* counter2, uint32_t value2, void* stream);
 int cmx_ctxmodels_run_late(cmx_ctxmodels_t*, void* box, size_t nbytes, float* probs, size_t pstride, uint32_t* sel, float* brk_dist,
                            const float** brk_dist0_out, void* stream);
 int cmx_bytemodel_late_run(int device, void* box, size_t nbytes, const float* brk0, const float* brk, const float* ppmd, const float* lstm0, const float* lstm,

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Who slows whom: every stage timed alone and next to each other stage on one GPU (round 5; the LSTM runs at 2.2 us/bit alone and at
 4.6 in the pipeline). One thread per stage, each with its own handle and HIP stream, looping over its own stand-alone workload; the
-measured stage's time per bit is taken while the partner loops.   python scripts/gpu_contention.py [partners]
-CMX_LSTM_SLEEP=1 / CMX_MIXNET_SLEEP=1 / CMX_MIXNET_PAD=1 select the poll variants of the library."""
+measured stage's time per bit is taken while the partner loops.   python scripts/gpu_contention.py [partners]"""
 import os
 import sys
 import threading

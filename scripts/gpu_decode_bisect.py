@@ -43,7 +43,7 @@ def main():
         n, seed = (int(x) for x in z["text50k_c_seed"])
     payload = synth.enwik_like(n, seed)
     libs = [("tree", None), ("tree (again)", None)] + [(os.path.basename(os.path.normpath(p)), os.path.abspath(p)) for p in sys.argv[1:]]
-    extra = [("tree, CMX_LATE_PULL=1", None, {"CMX_LATE_PULL": "1"}), ("tree, CMX_LATE_LSTM_PER_BYTE=1", None, {"CMX_LATE_LSTM_PER_BYTE": "1"})]
+    extra = [("tree, CMX_LATE_PULL=1", None, {"CMX_LATE_PULL": "1"})]
     with tempfile.TemporaryDirectory() as d:
         refp = None
         if os.path.exists(REF):

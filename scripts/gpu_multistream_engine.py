@@ -1,7 +1,6 @@
 """Throughput mode with the FULL ensemble: S independent streams on ONE GPU, one host thread each, aggregate input bytes/s.
 Every stream compresses the same payload (the bench shard's first N bytes), so every file can be checked against the one-stream result.
-The engines are constructed before the clock starts.   Usage: python scripts/gpu_multistream_engine.py 1,2,3 [payload_bytes]
-(CMX_MIXNET_SPEC=0 selects the one-workgroup mixing-network kernel: 68 instead of 94 workgroups per stream.)"""
+The engines are constructed before the clock starts.   Usage: python scripts/gpu_multistream_engine.py 1,2,3 [payload_bytes]"""
 import hashlib, json, os, sys, threading, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
@@ -33,7 +32,7 @@ for S in counts:
     dt = time.perf_counter() - t0
     shas = [hashlib.sha256(b).hexdigest()[:16] for b in blobs]
     want = want or shas[0]
-    print(json.dumps({"streams": S, "bytes_each": len(stream), "seconds": round(dt, 3), "aggregate_bytes_per_s": round(S * len(stream) / dt), "mixnet_spec": os.environ.get("CMX_MIXNET_SPEC", "1"),
+    print(json.dumps({"streams": S, "bytes_each": len(stream), "seconds": round(dt, 3), "aggregate_bytes_per_s": round(S * len(stream) / dt),
                       "file_bytes": len(blobs[0]), "sha256_16": shas[0], "all_files_identical": all(s == want for s in shas)}), flush=True)
     for e in engines:
         e.close() if hasattr(e, "close") else None
