@@ -13,11 +13,14 @@
 #include <string.h>
 #include <stddef.h>
 #include <string>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #include "../../include/cmix_amd.h"
 #include "mixnet_state.h"
 #include "cmx_late.h"
+#include "cmx_streams.h"
 
 extern "C" __global__ void cmx_mixnet_kernel(MixState*, const float*, const uint32_t*,
                                              const uint8_t*, const float*, int, float*, float*, int);
@@ -92,12 +95,6 @@ void build_sse_tables(std::vector<uint16_t>& t_st, std::vector<uint16_t>& t_sq) 
 }  // namespace
 
 void cmx_set_err(const std::string& s) { set_err(s); }  // shared with the other stage files
-
-// HIP maps a process's streams onto 4 hardware queues unless told otherwise, which serialises the stage kernels of one input
-// stream that are meant to overlap (3.3 -> 6.2 KB/s when it was found). The runtime reads the variable at its
-// first API call, so setting it when the library is loaded covers every host program (the reference's own main() included);
-// a value the user has set is left alone.
-__attribute__((constructor)) static void cmx_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
 
 struct cmx_mixnet {
   int device = 0;
@@ -216,7 +213,7 @@ void cmx_mixnet_destroy(cmx_mixnet_t* h) {
   if (h->ev0) hipEventDestroy(h->ev0);
   if (h->ev1) hipEventDestroy(h->ev1);
   for (int i = 0; i < CMX_PIPELINE_SLOTS; ++i) { if (h->ev_decay[i]) hipEventDestroy(h->ev_decay[i]); if (h->ev_kdone[i]) hipEventDestroy(h->ev_kdone[i]); }
-  if (h->own_up && h->s_up) hipStreamDestroy(h->s_up);
+  if (h->own_up && h->s_up) cmx_destroy_stream(h->s_up);
   delete h;
 }
 
@@ -355,10 +352,20 @@ int cmx_mixnet_spec_stats(cmx_mixnet_t* h, uint64_t out[5]) {
   return 0;
 }
 
-// A HIP stream for a stage's kernels. With the mixing network placed on one XCD through a compute-unit mask (CMX_MIXNET_XCD=k CMX_CUMASK=1) the network's
+// Every HIP stream of the library comes from this factory (tests/test_stream_factory.py keeps it so). HIP multiplexes a process's
+// plain streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless the environment says otherwise, and it is read once, when the
+// runtime starts: often before this library is loaded), and kernels of streams that share a queue run one after the other -- the
+// stage kernels of one input stream are meant to overlap. A stream created with a compute-unit mask is never pooled:
+// it gets a hardware queue of its own whatever the environment says. So every stream here carries a mask, the device's full one
+// unless the mixing network is placed on one XCD (CMX_MIXNET_XCD=k CMX_CUMASK=1, below), and the queues the library holds are
+// counted: at most CMX_MAX_HW_QUEUES per device and process (past ~24 active queues the hardware scheduler time-slices them,
+// profiles/r01_multiproc.txt).
+//
+// With the mixing network placed on one XCD through a compute-unit mask (CMX_MIXNET_XCD=k CMX_CUMASK=1) the network's
 // stream may use ONLY that XCD's compute units and every other stage's stream everything BUT them: a stage whose workgroups land on the crowded XCD is held
 // up there (profiles/r05_xcd_placement.txt: the LSTM's block kernels 4.7 -> 6.5 us/bit next to 27 spinning workgroups, whichever XCD). Bit i of the mask is
-// compute unit i / 8 of XCC i % 8 (the KFD spreads a queue's mask over the XCCs bit by bit). which: 0 = any other stage, 1 = the mixing network.
+// compute unit i / 8 of XCC i % 8 (the KFD spreads a queue's mask over the XCCs bit by bit). which: 0 = any other stage, 1 = the mixing network,
+// 2 = an upload stream (copies only; its own queue all the same, so that no copy waits behind a stage kernel).
 static bool g_cumask_applied = false;   // at least one masked stream was really created (the kernels' placement flag follows THIS, not the environment: advisor, round 5)
 static bool cumask_wanted() {
   static const char* const xe = getenv("CMX_MIXNET_XCD");
@@ -367,20 +374,101 @@ static bool cumask_wanted() {
   static const bool w = getenv("CMX_CUMASK") != nullptr && xe && atoi(xe) >= 0 && atoi(xe) < 8 && getenv("CMX_PIPELINE_STREAMS") == nullptr;
   return w;
 }
+namespace {
+std::mutex g_q_mu;
+std::map<hipStream_t, int> g_q_dev;   // every stream the factory made -> its device
+int g_q_held[64];                     // dedicated hardware queues held per device
+}  // namespace
 int cmx_make_stream(hipStream_t* st, int which) {
-  static const char* const xe = getenv("CMX_MIXNET_XCD");
-  const bool masked = cumask_wanted();
-  if (masked) {
-    const int x = atoi(xe);
-    uint32_t m[8];
-    for (int w = 0; w < 8; ++w) {
-      m[w] = 0;
-      for (int b = 0; b < 32; ++b) { const int cu = 32 * w + b; if (((cu & 7) == x) == (which == 1)) m[w] |= 1u << b; }
-    }
-    if (hipExtStreamCreateWithCUMask(st, 8, m) == hipSuccess) { if (which == 1) g_cumask_applied = true; return 0; }
-    (void)hipGetLastError();
+  *st = nullptr;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0 || cus > 32 * 32) {
+    set_err("cmx_make_stream: no device"); return 1;
   }
-  return hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess ? 0 : 1;
+  std::lock_guard<std::mutex> g(g_q_mu);
+  int& held = g_q_held[dev & 63];
+  if (held + 1 > CMX_MAX_HW_QUEUES) {
+    set_err("cmx_make_stream: this process already holds " + std::to_string(held) + " dedicated hardware queues on device " + std::to_string(dev) + ", the limit is " +
+            std::to_string(CMX_MAX_HW_QUEUES) + " (an engine takes 13, 14 when it decodes; CMX_PIPELINE_STREAMS=2 or 1 takes 8 or 6)");
+    return 1;
+  }
+  const int words = (cus + 31) / 32;
+  std::vector<uint32_t> full(words, 0u);
+  for (int cu = 0; cu < cus; ++cu) full[cu / 32] |= 1u << (cu % 32);
+  hipError_t e = hipErrorUnknown;
+  if (cumask_wanted() && which != 2) {
+    static const int x = atoi(getenv("CMX_MIXNET_XCD"));
+    std::vector<uint32_t> m(words, 0u);
+    for (int cu = 0; cu < cus; ++cu) if (((cu & 7) == x) == (which == 1)) m[cu / 32] |= 1u << (cu % 32);
+    e = hipExtStreamCreateWithCUMask(st, (uint32_t)words, m.data());
+    if (e == hipSuccess) { if (which == 1) g_cumask_applied = true; }
+    else (void)hipGetLastError();   // the diagnostic placement is not available: the full mask
+  }
+  if (e != hipSuccess) e = hipExtStreamCreateWithCUMask(st, (uint32_t)words, full.data());
+  if (e != hipSuccess) { *st = nullptr; set_err(std::string("cmx_make_stream: hipExtStreamCreateWithCUMask: ") + hipGetErrorString(e)); return 1; }
+  g_q_dev[*st] = dev;
+  ++held;
+  return 0;
+}
+// The one way a stream of the factory goes: destroyed, and its hardware queue given back to the budget. (Streams the caller owns are never passed here.)
+void cmx_destroy_stream(hipStream_t st) {
+  if (!st) return;
+  {
+    std::lock_guard<std::mutex> g(g_q_mu);
+    auto it = g_q_dev.find(st);
+    if (it != g_q_dev.end()) { --g_q_held[it->second & 63]; g_q_dev.erase(it); }
+  }
+  (void)hipStreamDestroy(st);
+}
+// dedicated hardware queues the library holds on a device (its streams)
+int cmx_hw_queues(int device) {
+  std::lock_guard<std::mutex> g(g_q_mu);
+  return g_q_held[device & 63];
+}
+
+// The overlap probe: one single-wave kernel per stream, each counts itself in and waits -- bounded by the wall clock -- until all n have
+// arrived, then records how many it saw. Kernels of streams that share a hardware queue cannot all be resident at once: the first one
+// waits out its bound and sees fewer than n. Vector memory operations only.
+__global__ void cmx_overlap_probe_kernel(unsigned* cnt, unsigned* seen, int i, unsigned n, unsigned long long ticks) {
+  if (threadIdx.x != 0) return;
+  __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned long long t0 = wall_clock64();
+  unsigned c = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  while (c < n && wall_clock64() - t0 < ticks) { __builtin_amdgcn_s_sleep(8); c = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __hip_atomic_store(seen + i, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// Runs the probe on n distinct streams of the current device (duplicates are dropped: roles that share a stream in the compact modes) and
+// synchronises them. Returns -1 on a device error, else the number of streams whose kernel saw every other one running beside it
+// (*distinct: how many were probed). ~50 ms per kernel that waits out its bound.
+int cmx_overlap_probe(const hipStream_t* st, int n, int* distinct) {
+  std::vector<hipStream_t> q;
+  for (int i = 0; i < n; ++i) {
+    if (!st[i]) continue;
+    bool dup = false;
+    for (hipStream_t s : q) dup = dup || s == st[i];
+    if (!dup) q.push_back(st[i]);
+  }
+  if (distinct) *distinct = (int)q.size();
+  if (q.empty()) return 0;
+  int dev = 0, khz = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) { set_err("cmx_overlap_probe: no device"); return -1; }
+  const int m = (int)q.size();
+  unsigned* d = nullptr;   // [0] the arrival counter, [1 + i] what stream i's kernel saw
+  if (hipMalloc((void**)&d, (size_t)(1 + m) * 4) != hipSuccess) { set_err("cmx_overlap_probe: hipMalloc failed"); return -1; }
+  bool ok = hipMemsetAsync(d, 0, (size_t)(1 + m) * 4, q[0]) == hipSuccess && hipStreamSynchronize(q[0]) == hipSuccess;
+  const unsigned long long ticks = 50ull * (unsigned long long)khz;   // 50 ms of the wall clock
+  for (int i = 0; ok && i < m; ++i) {
+    hipLaunchKernelGGL(cmx_overlap_probe_kernel, dim3(1), dim3(64), 0, q[i], d, d + 1, i, (unsigned)m, ticks);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  for (hipStream_t s : q) ok = hipStreamSynchronize(s) == hipSuccess && ok;
+  std::vector<unsigned> seen(m, 0u);
+  ok = ok && hipMemcpy(seen.data(), d + 1, (size_t)m * 4, hipMemcpyDeviceToHost) == hipSuccess;
+  (void)hipFree(d);
+  if (!ok) { set_err("cmx_overlap_probe: device error"); return -1; }
+  int all = 0;
+  for (unsigned c : seen) all += c >= (unsigned)m;
+  return all;
 }
 int cmx_cumask_on(void) { return cumask_wanted() && g_cumask_applied; }   // the mixing network's stream really carries its one-XCD mask
 
@@ -416,7 +504,7 @@ int cmx_mixnet_mode(cmx_mixnet_t* h) { return h && h->tolerance ? 1 : 0; }
 
 int cmx_mixnet_set_upload_stream(cmx_mixnet_t* h, void* stream) {
   if (!h) { set_err("cmx_mixnet_set_upload_stream: null handle"); return 1; }
-  if (h->own_up && h->s_up) hipStreamDestroy(h->s_up);
+  if (h->own_up && h->s_up) cmx_destroy_stream(h->s_up);
   h->s_up = (hipStream_t)stream; h->own_up = false;
   return 0;
 }
@@ -456,7 +544,7 @@ int cmx_mixnet_late_prepare(cmx_mixnet_t* h, size_t nbits) {
       h->d_late_mix = (float*)p;
     }
   }
-  if (!h->s_up) { if (hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking) != hipSuccess) { set_err("cmx_mixnet_late_prepare: stream creation failed"); return 1; } h->own_up = true; }
+  if (!h->s_up) { if (cmx_make_stream(&h->s_up, 2)) return 1; h->own_up = true; }
   return ensure_decay(h, nbits);
 }
 static int mixnet_run_impl(cmx_mixnet_t* h, const float* d_probs, const uint32_t* d_sel, const uint8_t* d_bits, size_t nbits, float* d_p_out, float* d_mix_out,
@@ -477,7 +565,7 @@ static int mixnet_run_impl(cmx_mixnet_t* h, const float* d_probs, const uint32_t
   // and on this hardware a host-to-device copy that waits in stream order holds up every later copy of the process (the
   // other stages' uploads of chunks further ahead: their kernels then start a mixing-network period late).
   if (ensure_decay(h, nbits)) return 1;
-  if (!h->s_up) { HIP_OK(hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking)); h->own_up = true; }
+  if (!h->s_up) { if (cmx_make_stream(&h->s_up, 2)) return 1; h->own_up = true; }
   const int slot = (int)(h->runs++ % CMX_PIPELINE_SLOTS);
   if (h->decay_used[slot]) HIP_OK(hipEventSynchronize(h->ev_kdone[slot]));   // the kernel that read this slot (implies its copy)
   float* hd = h->h_decay + (size_t)slot * h->decay_cap;

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "../../include/cmix_amd.h"
+#include "cmx_streams.h"
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
 
@@ -194,7 +195,7 @@ void free_perbit(cmx_engine* h) {
   h->d_lstm_next = nullptr; h->d_hint = nullptr; h->d_p = nullptr; h->d_scratch = nullptr; h->d_scratch_sel = nullptr;
   if (h->pin) (void)hipHostFree(h->pin);
   h->pin = nullptr;
-  if (h->st) (void)hipStreamDestroy(h->st);
+  if (h->st) cmx_destroy_stream(h->st);
   h->st = nullptr;
   cmx_mixnet_destroy(h->mix); h->mix = nullptr;
   cmx_lstm_destroy(h->lstm); h->lstm = nullptr;
@@ -213,7 +214,7 @@ int ensure_perbit(cmx_engine* h, const char* where) {
   h->ppmd = h->mix ? cmx_ppmd_create(h->vocab) : nullptr;
   if (!h->ppmd) { free_perbit(h); return 1; }  // the failing stage has set the error
   bool ok = hipSetDevice(h->device) == hipSuccess;
-  ok = ok && hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess;
+  if (ok && cmx_make_stream(&h->st, 0)) { free_perbit(h); return 1; }   // the factory has said why
   ok = ok && hipHostMalloc((void**)&h->pin, sizeof(Pinned), hipHostMallocDefault) == hipSuccess;
   ok = ok && hipMalloc((void**)&h->d_byte, 16) == hipSuccess;
   ok = ok && hipMalloc((void**)&h->d_rows, 8 * CMX_N_INPUTS * 4) == hipSuccess;

@@ -19,6 +19,7 @@
 #include "../../include/cmix_amd.h"
 #include "fxcm_build.h"
 #include "cmx_late.h"
+#include "cmx_streams.h"
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
 extern "C" int cmx_device_count(void);
@@ -910,7 +911,7 @@ void cmx_fxcm_destroy(cmx_fxcm_t* h) {
   if (h->d_prof) (void)hipFree(h->d_prof);
   if (h->d_xfer) (void)hipFree(h->d_xfer);
   for (hipEvent_t e : h->ev_up) if (e) (void)hipEventDestroy(e);
-  if (h->own_up && h->s_up) (void)hipStreamDestroy(h->s_up);
+  if (h->own_up && h->s_up) cmx_destroy_stream(h->s_up);
   if (h->d_rows) (void)hipFree(h->d_rows);
   for (FxByteRec* r : h->late_recs) cmx_late_free(r);
   for (FxByteRec* r : h->late_drecs) cmx_late_free_dev(r);
@@ -964,7 +965,7 @@ int cmx_fxcm_run(cmx_fxcm_t* h, const uint8_t* bytes, const uint8_t* d_bytes, si
   // the records go up on the upload stream (nothing in front of them), the kernel's stream waits for the copy: enqueued on
   // `s` the copy would sit behind the previous chunk's kernel, and a host-to-device copy that waits in stream order holds up
   // every later copy of the process
-  if (!h->s_up) { if (hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking) != hipSuccess) { cmx_set_err("cmx_fxcm_run: stream creation failed"); return 1; } h->own_up = true; }
+  if (!h->s_up) { if (cmx_make_stream(&h->s_up, 2)) return 1; h->own_up = true; }
   if (hipMemcpyAsync(h->d_recs[b], h->h_recs[b], nbytes * sizeof(FxByteRec), hipMemcpyHostToDevice, h->s_up) != hipSuccess ||
       hipEventRecord(h->ev_up[b], h->s_up) != hipSuccess || hipStreamWaitEvent(s, h->ev_up[b], 0) != hipSuccess) { cmx_set_err("cmx_fxcm_run: record upload failed"); return 1; }
   if (h->rows_cap < nbytes) {   // grown between chunks: nothing of this stream may be in flight on the old buffer
@@ -1046,7 +1047,7 @@ int cmx_fxcm_profile(cmx_fxcm_t* h, unsigned long long out64[128]) {
 
 int cmx_fxcm_set_upload_stream(cmx_fxcm_t* h, void* stream) {
   if (!h) { cmx_set_err("cmx_fxcm_set_upload_stream: null handle"); return 1; }
-  if (h->own_up && h->s_up) (void)hipStreamDestroy(h->s_up);
+  if (h->own_up && h->s_up) cmx_destroy_stream(h->s_up);
   h->s_up = (hipStream_t)stream; h->own_up = false;
   return 0;
 }

@@ -31,10 +31,10 @@
 #include "p8cm2v2_dev.h"
 #include "p8stage_build.h"
 #include "cmx_late.h"
+#include "cmx_streams.h"
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
 extern "C" int cmx_device_count(void);
-extern "C" int cmx_make_stream(hipStream_t* st, int which);   // cmx_api.hip: a stage's kernel stream (compute-unit mask when the mixing network owns an XCD)
 
 // ---------------------------------------------------------------- role kernels
 // skip: chunk-local steps before the stream's first byte boundary (the maps have no contexts yet, reference :1072 loop over cn == 0)
@@ -1311,13 +1311,13 @@ void cmx_p8stage_destroy(cmx_p8stage_t* h) {
     for (hipStream_t q : {h->s_a, h->s_b, h->s_c, h->s_d, h->s_e, h->s_m, h->s_f}) {
       bool dup = !q;
       for (int i = 0; i < ns; i++) dup = dup || seen[i] == q;
-      if (!dup) { seen[ns++] = q; (void)hipStreamDestroy(q); }
+      if (!dup) { seen[ns++] = q; cmx_destroy_stream(q); }
     }
   }
   if (h->d_prx) (void)hipFree(h->d_prx);
   for (auto& b : h->late) { cmx_late_free(b.rec); cmx_late_free_dev(b.d_rec); cmx_late_free_dev(b.x); cmx_late_free_dev(b.order); }
   if (h->h_mixfail) (void)hipHostFree(h->h_mixfail);
-  if (h->own_up && h->s_up) (void)hipStreamDestroy(h->s_up);
+  if (h->own_up && h->s_up) cmx_destroy_stream(h->s_up);
   for (hipEvent_t e : {h->ev_up, h->ev_ord, h->ev_a, h->ev_b, h->ev_c, h->ev_e, h->ev_f}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev_mix) if (e) (void)hipEventDestroy(e);
   if (h->front) p8f_front_free(h->front);
@@ -1368,6 +1368,7 @@ cmx_p8stage_t* cmx_p8stage_create(int device) {
     // stream: the stage's period grows to their sum, the stream count is what many engines per GPU need.
     const char* ns = getenv("CMX_PIPELINE_STREAMS");
     const int mode = ns && ns[0] == '2' ? 2 : ns && ns[0] == '1' ? 1 : 0;
+    const bool ok_before = ok;
     for (hipStream_t* q : {&h->s_a, &h->s_d, &h->s_m}) ok = ok && cmx_make_stream(q, 0) == 0;
     if (mode == 0) for (hipStream_t* q : {&h->s_b, &h->s_e}) ok = ok && cmx_make_stream(q, 0) == 0;
     else { h->s_b = h->s_d; h->s_e = h->s_d; }
@@ -1375,6 +1376,7 @@ cmx_p8stage_t* cmx_p8stage_create(int device) {
     else ok = ok && cmx_make_stream(&h->s_c, 0) == 0;
     if (mode == 0) ok = ok && cmx_make_stream(&h->s_f, 0) == 0;   // the DMC forest beside the small learners
     else h->s_f = h->s_c;
+    if (ok_before && !ok) { cmx_p8stage_destroy(h); return nullptr; }   // cmx_make_stream has said why (the device's queue budget)
   }
   for (hipEvent_t* e : {&h->ev_up, &h->ev_ord, &h->ev_a, &h->ev_b, &h->ev_c, &h->ev_e, &h->ev_f}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
   for (hipEvent_t& e : h->ev_mix) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
@@ -1464,7 +1466,7 @@ int cmx_p8stage_run(cmx_p8stage_t* h, const uint8_t* bytes, size_t nbytes, float
   if (h->mix_used[par]) for (hipStream_t q : {h->s_a, h->s_b, h->s_c, h->s_d, h->s_e, h->s_f}) ok = ok && hipStreamWaitEvent(q, h->ev_mix[par], 0) == hipSuccess;   // the mixer that last read these rows
   // upload on the upload stream: on s_d the copy would sit behind the previous chunk's order-N kernel, and a host-to-device
   // copy that waits in stream order holds up every later copy of the process
-  if (!h->s_up) { ok = ok && hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking) == hipSuccess; h->own_up = true; }
+  if (!h->s_up) { ok = ok && cmx_make_stream(&h->s_up, 2) == 0; h->own_up = true; }
   ok = ok && hipMemcpyAsync(b.d, b.h, b.total, hipMemcpyHostToDevice, h->s_up) == hipSuccess;
   ok = ok && hipEventRecord(h->ev_up, h->s_up) == hipSuccess;
   ok = ok && hipStreamWaitEvent(h->s_d, h->ev_up, 0) == hipSuccess;
@@ -1737,9 +1739,15 @@ int cmx_p8stage_debug_set_pos(cmx_p8stage_t* h, int pos) {
 }
 int cmx_p8stage_mixfail(cmx_p8stage_t* h) { return h && h->h_mixfail && *h->h_mixfail ? 1 : 0; }
 
+// the stage's role streams (for the pipeline's overlap probe); shared ones appear once per role
+int cmx_p8stage_streams(cmx_p8stage_t* h, hipStream_t* out, int cap) {
+  int n = 0;
+  if (h) for (hipStream_t q : {h->s_a, h->s_b, h->s_c, h->s_d, h->s_e, h->s_f, h->s_m}) if (n < cap) out[n++] = q;
+  return n;
+}
 int cmx_p8stage_set_upload_stream(cmx_p8stage_t* h, void* stream) {
   if (!h) { cmx_set_err("cmx_p8stage_set_upload_stream: null handle"); return 1; }
-  if (h->own_up && h->s_up) (void)hipStreamDestroy(h->s_up);
+  if (h->own_up && h->s_up) cmx_destroy_stream(h->s_up);
   h->s_up = (hipStream_t)stream; h->own_up = false;
   return 0;
 }

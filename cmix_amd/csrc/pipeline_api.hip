@@ -26,9 +26,11 @@
 
 #include "../../include/cmix_amd.h"
 #include "cmx_late.h"
+#include "cmx_streams.h"
+
+extern "C" int cmx_p8stage_streams(cmx_p8stage_t* h, hipStream_t* out, int cap);   // p8stage.hip: the role streams
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
-extern "C" int cmx_make_stream(hipStream_t* st, int which);   // cmx_api.hip: a stage's kernel stream (compute-unit mask when the mixing network owns an XCD)
 static double late_now();   // ms on the steady clock (defined with the late-bit pipeline below)
 
 // ---- construction ahead of time ------------------------------------------------------------------------------
@@ -191,6 +193,8 @@ struct cmx_pipeline {
   int compact = 0;       // CMX_PIPELINE_STREAMS: 0 = one stream per stage / role, 2 and 1 = throughput modes with fewer hardware queues per engine
   bool failed = false;   // sticky: a chunk failed after its stages had begun to be enqueued (the stream's state is void)
   int wgs = 0;           // workgroups this engine's persistent kernels keep resident (wg_claim)
+  int overlap = -1;      // the last overlap probe (probe_streams): 1 every stream ran beside all the others, 0 not, -1 not run / device error
+  int probe_all = 0, probe_n = 0;   // ... how many of how many distinct streams saw all the others
   double host_ms[6] = {0, 0, 0, 0, 0, 0};   // calling thread, since the last reset: slot wait, PPMd, ctx + LSTM enqueue, fxcm (parser + enqueue), paq8 (front end + enqueue), mixing network enqueue
   Slot slot[kSlots];
   uint64_t chunks = 0;    // chunks begun
@@ -219,6 +223,18 @@ void collect(cmx_pipeline* h, Slot& s) {  // the slot's chunk has finished (its 
   s.untimed = false;
 }
 }  // namespace
+
+// The overlap probe on every stream of the handle (include/cmix_amd.h, cmx_pipeline_stage_overlap): the stage streams, the upload stream,
+// paq8's role streams and, in a decoder, the byte model's.
+static int probe_streams(cmx_pipeline* h) {
+  hipStream_t q[24] = {h->s_lstm, h->s_ctx, h->s_mix, h->s_up, h->s_fx, h->s_p8, h->late ? h->late->s_bm : nullptr};
+  int n = 7;
+  if (h->p8) n += cmx_p8stage_streams(h->p8, q + n, 24 - n);
+  const int all = cmx_overlap_probe(q, n, &h->probe_n);
+  h->probe_all = all < 0 ? 0 : all;
+  h->overlap = all < 0 ? -1 : all == h->probe_n ? 1 : 0;
+  return h->overlap;
+}
 
 __global__ void cmx_fxcm_hints_kernel(const float* layer0, long stride, const float* p_after, const int* ex, int T, int16_t* lstmpr, uint8_t* lstmex) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -268,7 +284,7 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
       cmx_late_free_dev(q.cnt); cmx_late_free_dev(q.layer0); cmx_late_free_dev(q.sel); cmx_late_free_dev(q.brk); cmx_late_free_dev(q.lstm);
       cmx_late_free_dev(q.hint_pr); cmx_late_free_dev(q.hint_ex);
     }
-    if (h->late->s_bm) (void)hipStreamDestroy(h->late->s_bm);
+    if (h->late->s_bm) cmx_destroy_stream(h->late->s_bm);
     if (h->late->dbg_row) (void)hipHostFree(h->late->dbg_row);
     if (h->late->dbg_sel) (void)hipHostFree(h->late->dbg_sel);
     delete h->late;
@@ -295,13 +311,13 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
     for (hipEvent_t e : {s.ev_in, s.ev_ctx0, s.ev_ctx1, s.ev_lstm0, s.ev_lstm1, s.ev_mix0, s.ev_mix1, s.ev_cols})
       if (e) (void)hipEventDestroy(e);
   }
-  if (h->s_ctx && h->s_ctx != h->s_lstm) (void)hipStreamDestroy(h->s_ctx);
-  if (h->s_lstm) (void)hipStreamDestroy(h->s_lstm);
-  if (h->s_mix) (void)hipStreamDestroy(h->s_mix);
-  if (h->s_up) (void)hipStreamDestroy(h->s_up);
-  if (h->s_fx && h->s_fx != h->s_lstm) (void)hipStreamDestroy(h->s_fx);
+  if (h->s_ctx && h->s_ctx != h->s_lstm) cmx_destroy_stream(h->s_ctx);
+  if (h->s_lstm) cmx_destroy_stream(h->s_lstm);
+  if (h->s_mix) cmx_destroy_stream(h->s_mix);
+  if (h->s_up) cmx_destroy_stream(h->s_up);
+  if (h->s_fx && h->s_fx != h->s_lstm) cmx_destroy_stream(h->s_fx);
   if (h->d_fx_scratch) (void)hipFree(h->d_fx_scratch);
-  if (h->s_p8 && h->s_p8 != h->s_mix) (void)hipStreamDestroy(h->s_p8);
+  if (h->s_p8 && h->s_p8 != h->s_mix) cmx_destroy_stream(h->s_p8);
   if (h->d_p8_scratch) (void)hipFree(h->d_p8_scratch);
   cmx_p8stage_destroy(h->p8);
   cmx_fxcm_destroy(h->fxcm);
@@ -338,7 +354,8 @@ cmx_pipeline_t* cmx_pipeline_create(const uint8_t vocab[256], int device, size_t
   if (two) h->s_ctx = h->s_lstm;
   else ok = ok && cmx_make_stream(&h->s_ctx, 0) == 0;
   ok = ok && cmx_make_stream(&h->s_mix, 1) == 0;
-  ok = ok && hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && cmx_make_stream(&h->s_up, 2) == 0;
+  if (!ok) { cmx_pipeline_destroy(h); return nullptr; }   // cmx_make_stream has said why (the device's queue budget)
   ok = ok && cmx_mixnet_set_upload_stream(h->mix, h->s_up) == 0;
   const size_t n = max_chunk_bytes;
   for (Slot& s : h->slot) {
@@ -358,6 +375,7 @@ cmx_pipeline_t* cmx_pipeline_create(const uint8_t vocab[256], int device, size_t
   }
   if (!ok) { cmx_set_err("cmx_pipeline_create: stream / buffer allocation failed"); cmx_pipeline_destroy(h); return nullptr; }
   for (int i = 0; i < 256; ++i) h->last_dist[i] = (float)(1.0 / 256);  // ByteModel constructor (byte-model.cpp:5-6)
+  if (probe_streams(h) < 0) { cmx_pipeline_destroy(h); return nullptr; }
   return h;
 }
 
@@ -380,7 +398,7 @@ int cmx_pipeline_enable_fxcm(cmx_pipeline_t* h, const char* dictionary_path) {
   const size_t n = h->max_chunk;
   bool ok = true;
   if (h->compact == 1) h->s_fx = h->s_lstm;   // throughput mode: LSTM, contexts and fxcm take turns on one stream
-  else ok = cmx_make_stream(&h->s_fx, 0) == 0;
+  else if (cmx_make_stream(&h->s_fx, 0)) { cmx_fxcm_destroy(fx); return 1; }   // (the factory has said why)
   ok = ok && hipMalloc((void**)&h->d_fx_scratch, 8 * n * 434 * sizeof(float)) == hipSuccess;
   for (Slot& s : h->slot) {
     ok = ok && hipMalloc((void**)&s.d_fx_pr, 8 * n * 2) == hipSuccess;
@@ -394,7 +412,7 @@ int cmx_pipeline_enable_fxcm(cmx_pipeline_t* h, const char* dictionary_path) {
       s.d_fx_pr = nullptr; s.d_fx_ex = nullptr;
       for (hipEvent_t* e : {&s.ev_fxin, &s.ev_fx0, &s.ev_fx1}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
     }
-    if (h->s_fx && h->s_fx != h->s_lstm) (void)hipStreamDestroy(h->s_fx);
+    if (h->s_fx && h->s_fx != h->s_lstm) cmx_destroy_stream(h->s_fx);
     if (h->d_fx_scratch) (void)hipFree(h->d_fx_scratch);
     h->s_fx = nullptr; h->d_fx_scratch = nullptr;
     cmx_fxcm_destroy(fx);
@@ -403,7 +421,7 @@ int cmx_pipeline_enable_fxcm(cmx_pipeline_t* h, const char* dictionary_path) {
   }
   (void)cmx_fxcm_set_upload_stream(fx, h->s_up);
   h->fxcm = fx;
-  return 0;
+  return probe_streams(h) < 0 ? 1 : 0;
 }
 
 // ---- the paq8 stage on the device (opt-in): layer-0 columns 434..2024 (include/cmix_amd.h section 2f) ------------
@@ -419,14 +437,14 @@ int cmx_pipeline_enable_paq8(cmx_pipeline_t* h) {
   if (!p8) return 1;
   bool ok = true;
   if (h->compact) h->s_p8 = h->s_mix;   // throughput mode: the mixing network's stream itself waits for the stage's mixer
-  else ok = cmx_make_stream(&h->s_p8, 0) == 0;
+  else if (cmx_make_stream(&h->s_p8, 0)) { cmx_p8stage_destroy(p8); return 1; }   // (the factory has said why)
   ok = ok && hipMalloc((void**)&h->d_p8_scratch, 8 * h->max_chunk * 1591 * sizeof(float)) == hipSuccess;
   for (Slot& s : h->slot)
     for (hipEvent_t* e : {&s.ev_p80, &s.ev_p81}) ok = ok && hipEventCreate(e) == hipSuccess;
   if (!ok) {
     for (Slot& s : h->slot)
       for (hipEvent_t* e : {&s.ev_p80, &s.ev_p81}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    if (h->s_p8 && h->s_p8 != h->s_mix) (void)hipStreamDestroy(h->s_p8);
+    if (h->s_p8 && h->s_p8 != h->s_mix) cmx_destroy_stream(h->s_p8);
     if (h->d_p8_scratch) (void)hipFree(h->d_p8_scratch);
     h->s_p8 = nullptr; h->d_p8_scratch = nullptr;
     cmx_p8stage_destroy(p8);
@@ -435,7 +453,7 @@ int cmx_pipeline_enable_paq8(cmx_pipeline_t* h) {
   }
   (void)cmx_p8stage_set_upload_stream(p8, h->s_up);
   h->p8 = p8;
-  return 0;
+  return probe_streams(h) < 0 ? 1 : 0;
 }
 // the mixing network's tolerance mode (cmx_mixnet_set_tolerance: NOT bit-exact, bench / measurement only); before the first chunk
 int cmx_pipeline_set_tolerance(cmx_pipeline_t* h, int on) {
@@ -450,6 +468,7 @@ int cmx_pipeline_set_tolerance(cmx_pipeline_t* h, int on) {
   return 0;
 }
 // 0 strict, 1 tolerance: not strict as soon as EITHER the mixing network or the LSTM computes in its tolerance form
+int cmx_pipeline_stage_overlap(cmx_pipeline_t* h) { return h ? h->overlap : -1; }
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t* h) { return !h ? -1 : (h->lstm_tolerance ? 1 : cmx_mixnet_mode(h->mix)); }
 // ---- diagnostics of a long run (scripts/gpu_long_run.py): all of them synchronise the device ----
 int cmx_pipeline_mixnet_rows(cmx_pipeline_t* h, uint32_t rows[47]) { return h ? cmx_mixnet_rows(h->mix, rows) : 1; }
@@ -845,7 +864,15 @@ int cmx_pipeline_late_start(cmx_pipeline_t* h, int last_bit) {
   Late* L = new Late();
   h->late = L;
   const size_t n = kLateChunk, T = 8 * n;
-  bool ok = hipStreamCreateWithFlags(&L->s_bm, hipStreamNonBlocking) == hipSuccess;
+  if (cmx_make_stream(&L->s_bm, 0)) { L->failed = true; return 1; }   // (the factory has said why)
+  // Every stage kernel of a decoder's chunk waits inside its launch for the others: on streams that share a hardware queue they would
+  // time out one after another. Refuse at once instead.
+  if (probe_streams(h) != 1) {
+    cmx_set_err("cmx_pipeline_late_start: only " + std::to_string(h->probe_all) + " of the engine's " + std::to_string(h->probe_n) +
+                " streams ran beside all the others (overlap probe): they share hardware queues, and a decoder needs every stage kernel running at once");
+    L->failed = true; return 1;
+  }
+  bool ok = true;
   ok = ok && hipHostMalloc((void**)&L->dbg_row, CMX_N_INPUTS * 4, hipHostMallocDefault) == hipSuccess && hipHostMalloc((void**)&L->dbg_sel, CMX_N_MIXERS * 4, hipHostMallocDefault) == hipSuccess;
   for (LateSet& q : L->set) {
     q.box = (CmxLateBox*)cmx_late_alloc(cmx_late_box_bytes(T));

@@ -152,6 +152,8 @@ def lib():
         L.cmx_probe_libm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         L.cmx_pipeline_set_tolerance.argtypes = [C.c_void_p, C.c_int]
         L.cmx_pipeline_mixnet_mode.argtypes = [C.c_void_p]
+        L.cmx_pipeline_stage_overlap.argtypes = [C.c_void_p]
+        L.cmx_hw_queues.argtypes = [C.c_int]
         L.cmx_mixnet_set_tolerance.argtypes = [C.c_void_p, C.c_int]
         L.cmx_mixnet_mode.argtypes = [C.c_void_p]
         L.cmx_pipeline_late_start.argtypes = [C.c_void_p, C.c_int]
@@ -168,6 +170,11 @@ def lib():
 
 def last_error():
     return lib().cmx_last_error().decode()
+
+
+def hw_queues(device=0):
+    """dedicated hardware queues (HIP streams, one queue each) the library holds on the device now"""
+    return lib().cmx_hw_queues(device)
 
 
 def device_count():
@@ -567,6 +574,14 @@ class Pipeline:
     def mixnet_mode(self):
         """0 strict (bit-exact, the default), 1 tolerance -- as the library reports it"""
         return lib().cmx_pipeline_mixnet_mode(self.h)
+
+    def stage_overlap(self):
+        """The last overlap probe (creation, enable_fxcm / enable_paq8, late_start): True when every stage stream of the handle ran beside all
+        the others, False when some share a hardware queue (the coded bytes are the same either way; a decoder refuses to start)."""
+        r = lib().cmx_pipeline_stage_overlap(self.h)
+        if r < 0:
+            raise CmxError("stage_overlap: the probe has not run or failed")
+        return r == 1
 
     # ---- the decoder's form (late-bit protocol, include/cmix_amd.h section 4): fxcm and paq8 must be enabled ----
     def late_start(self, last_bit=0):

@@ -338,9 +338,10 @@ int cmx_ppmd_run(cmx_ppmd_t*, const uint8_t* bytes, size_t nbytes, float* out_pr
  *    a chunk's latency through the stages is several chunk periods, the depth keeps every stage busy).
  * ------------------------------------------------------------------------ */
 /* Environment read by the engine (all optional):
- *   GPU_MAX_HW_QUEUES      (HIP's own) must be >= 14 before the first HIP call for the stages of one stream to overlap: an
- *                          engine uses 14 HIP streams (5 stages, upload, 7 paq8 roles, paq8 hand-over) and HIP maps streams
- *                          onto 4 hardware queues by default. The library sets 16 when it is loaded unless the variable is set.
+ *   GPU_MAX_HW_QUEUES      (HIP's own) not read, not set and not needed: every HIP stream of the library is created with a compute-unit
+ *                          mask (the device's full one), which HIP never pools onto its shared queues, so each stage stream has a
+ *                          hardware queue of its own whatever the variable says. An engine holds 13 (5 stages, upload, 7 paq8 roles),
+ *                          14 when it decodes (the byte model); at most CMX_MAX_HW_QUEUES per device and process (cmx_hw_queues()).
  *   CMX_PIPELINE_STREAMS   2 or 1: throughput mode for several streams per GPU -- fewer hardware queues per engine (8 or 6;
  *                          roles take turns on shared streams, the per-stream period grows)
  *   CMX_MIXNET_XCD=k       the mixing network's 27 workgroups on XCD k, hand-off words through that XCD's L2 (bit-exact either way)
@@ -354,6 +355,8 @@ int cmx_ppmd_run(cmx_ppmd_t*, const uint8_t* bytes, size_t nbytes, float* out_pr
  * _enable_paq8 keep count per device and refuse (cmx_last_error says why) an engine that would exceed the device's compute units.
  *   CMX_FXCM_PROFILE, CMX_P8FAM_PROFILE, CMX_MIXNET_DBG     in-kernel phase timers / timing experiments (scripts/gpu_*prof*) */
 #define CMX_PIPELINE_SLOTS 8   /* chunks in flight per stream (layer-0 matrices the caller cycles through) */
+#define CMX_MAX_HW_QUEUES 32   /* dedicated hardware queues the library holds per device and process; a stage that would go past it is refused */
+int cmx_hw_queues(int device);   /* the dedicated hardware queues (HIP streams) the library holds on the device now */
 /* Construction ahead of time: start building the vocabulary-independent stages of an engine for `device` -- mixing
  * network, paq8 stage and (with_fxcm != 0; dictionary_path as for cmx_pipeline_enable_fxcm) the fxcm stage, ~16 GB of tables -- on a
  * thread of the library, and return at once. The caller goes on with what has to precede the predictor (runner.cpp:166-202:
@@ -365,6 +368,11 @@ int cmx_prewarm(int device, const char* dictionary_path, int with_fxcm);
 typedef struct cmx_pipeline cmx_pipeline_t;
 cmx_pipeline_t* cmx_pipeline_create(const uint8_t vocab[256], int device, size_t max_chunk_bytes);
 void cmx_pipeline_destroy(cmx_pipeline_t*);
+/* The overlap probe (run by cmx_pipeline_create, _enable_fxcm, _enable_paq8 and cmx_pipeline_late_start): one tiny kernel on each of the
+ * handle's streams, each waiting (at most ~50 ms) for all the others to run beside it. 1: every stage stream ran concurrently with all the
+ * others at the last probe; 0: some did not (they share hardware queues: the stages of a chunk then run one after another -- the coded
+ * bytes are right either way, only the period grows; a decoder refuses to start); -1: bad handle. */
+int cmx_pipeline_stage_overlap(cmx_pipeline_t*);
 /* Code the next n <= max_chunk_bytes bytes of the stream.
  *   bytes    HOST   [n]
  *   d_layer0 DEVICE [8n][2078] f32: columns 3..2024 (fxcm, paq8 -- no stage yet) must already hold the
