@@ -21,6 +21,7 @@
 #include "mixnet_state.h"
 #include "cmx_late.h"
 #include "cmx_streams.h"
+#include "cmx_verify.h"
 
 extern "C" __global__ void cmx_mixnet_kernel(MixState*, const float*, const uint32_t*,
                                              const uint8_t*, const float*, int, float*, float*, int);
@@ -28,6 +29,11 @@ extern "C" __global__ void cmx_mixnet_spec_kernel(MixState*, SpecXfer*, const fl
                                                   float*, int);
 extern "C" __global__ void cmx_mixnet_spec_jitter_kernel(MixState*, SpecXfer*, const float*, const uint32_t*, const uint8_t*, const float*, int, float*, float*, int);
 extern "C" __global__ void cmx_mixnet_spec_late_kernel(MixState*, SpecXfer*, const float*, const uint32_t*, const float*, int, float*, float*, int, CmxLate);
+extern "C" __global__ void cmx_mixnet_spec_verify_kernel(MixState*, SpecXfer*, const float*, const uint32_t*, const uint8_t*, const float*, int, float*, float*, int,
+                                                         CmxVerify);
+extern "C" __global__ void cmx_mixnet_verify_kernel(const MixState*, const float*, const uint32_t*, const uint8_t*, const float*, int, CmxVerify);
+extern "C" __global__ void cmx_mixnet_verify_fold_kernel(CmxVerifyHdr*, unsigned long long, int);
+extern "C" __global__ void cmx_mixnet_verify_xor_kernel(void*, int, unsigned);
 extern "C" __global__ void cmx_sse_init_kernel(MixState*);
 extern "C" __global__ void cmx_probe_libm_kernel(int, const float*, float*, size_t);
 
@@ -135,7 +141,25 @@ struct cmx_mixnet {
   float* d_late_p = nullptr; size_t late_p_cap = 0;   // the decoder's form: the kernel's p[] array (the host reads p from the box)
   float* late_mix_cur[3] = {nullptr, nullptr, nullptr};
   float* d_late_mix = nullptr;                         // CMX_LATE_DEBUG=1: the 47 mixer outputs per bit of the chunk launched last (test hook)
+  bool verify = false;                                 // cmx_mixnet_set_verify: every chunk through the VERIFY kernel + cmx_mixnet_verify_kernel (cmx_verify.h)
+  CmxVerifyHdr* d_vhdr = nullptr;                      // its sticky record and the launch's mismatch words
+  unsigned long long* d_vrec = nullptr; size_t vrec_blocks = 0;   // [blocks][CMX_VERIFY_REC] consumed sums of a launch
+  unsigned long long* d_vseg = nullptr;                // [26][10001][4] digests of the stored layer-0 row segments
+  struct { int cls = 0; uint64_t bit = 0, index = 0; uint32_t mask = 0; } pert;   // cmx_mixnet_debug_verify_perturb (cls 0: none armed)
 };
+
+// What a verify record (cmx_mixnet_verify_report's eight words) says, for an error message
+std::string cmx_mixnet_verify_text(const unsigned long long r[8]) {
+  static const char* const names[CMX_VC_N] = {"?", "layer-0 row (raw inputs)", "coded bit", "selectors", "decay (gather wave)", "decay (tail-a wave)",
+                                              "decay (tail-b wave)", "ring written (stretched inputs)", "ring read (stretched inputs)", "layer-0 row segment"};
+  const unsigned cls = r[3] < CMX_VC_N ? (unsigned)r[3] : 0;
+  std::string s = "verify mode: " + std::to_string(r[2]) + " mismatch(es) between what the mixing network consumed and its source; the first: " + names[cls] +
+                  ", in the block of " + std::to_string(CMX_VERIFY_BLOCK) + " bits from stream bit " + std::to_string(r[4]);
+  if (r[5] != ~0ull) s += ", mixer " + std::to_string(r[5]);
+  if (r[6] != ~0ull) s += ", row " + std::to_string(r[6]);
+  if (r[7] != ~0ull) s += ", segment " + std::to_string(r[7]);
+  return s + " (the stream's output is void)";
+}
 
 extern "C" {
 
@@ -295,7 +319,8 @@ cmx_mixnet_t* cmx_mixnet_create(int device) {
   }
   h->d_xfer = (SpecXfer*)dalloc(sizeof(SpecXfer), true);   // incl. the zero padding of the input ring
   bool attr_ok = true;
-  for (const void* k : {(const void*)cmx_mixnet_spec_kernel, (const void*)cmx_mixnet_spec_jitter_kernel, (const void*)cmx_mixnet_spec_late_kernel})
+  for (const void* k : {(const void*)cmx_mixnet_spec_kernel, (const void*)cmx_mixnet_spec_jitter_kernel, (const void*)cmx_mixnet_spec_late_kernel,
+                        (const void*)cmx_mixnet_spec_verify_kernel})
     attr_ok = attr_ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CMX_SPEC_LDS_BYTES) == hipSuccess;
   if (!h->d_xfer || !attr_ok) {
     set_err("cmx_mixnet_create: hand-off area / kernel attribute (spec kernel) failed");
@@ -480,7 +505,63 @@ int cmx_cumask_on(void) { return cumask_wanted() && g_cumask_applied; }   // the
 int cmx_mixnet_set_tolerance(cmx_mixnet_t* h, int on) {
   if (!h) { set_err("cmx_mixnet_set_tolerance: null handle"); return 1; }
   if (h->runs || h->bits_done) { set_err("cmx_mixnet_set_tolerance: only before the first bit of the stream"); return 1; }
+  if (on && h->verify) { set_err("cmx_mixnet_set_tolerance: verify mode is on (it checks the strict kernel)"); return 1; }
   h->tolerance = on != 0;
+  return 0;
+}
+// Verify mode (opt-in, strict look-ahead chunks only): see include/cmix_amd.h. Allocates the verify area (~8.5 MB) when first switched on.
+int cmx_mixnet_set_verify(cmx_mixnet_t* h, int on) {
+  const int fail_value = 1;
+  if (!h) { set_err("cmx_mixnet_set_verify: null handle"); return 1; }
+  if (h->runs || h->bits_done) { set_err("cmx_mixnet_set_verify: only before the first bit of the stream"); return 1; }
+  if (on && h->tolerance) { set_err("cmx_mixnet_set_verify: the tolerance switch is set (verify mode checks the strict kernel)"); return 1; }
+  if (on && h->late_p_cap) { set_err("cmx_mixnet_set_verify: this handle runs the decoder's (late) kernel, which verify mode does not cover"); return 1; }
+  if (on && !h->d_vhdr) {
+    HIP_OK(hipSetDevice(h->device));
+    const size_t seg_bytes = (size_t)CMX_MIX0 * CMX_ROWS_PER_MIXER * CMX_VERIFY_SEGS * 8;
+    void* a = nullptr; void* b = nullptr;
+    HIP_OK(hipMalloc(&a, sizeof(CmxVerifyHdr)));
+    h->allocs.push_back(a);
+    HIP_OK(hipMalloc(&b, seg_bytes));
+    h->allocs.push_back(b);
+    HIP_OK(hipMemset(a, 0, sizeof(CmxVerifyHdr)));
+    HIP_OK(hipMemset(b, 0, seg_bytes));
+    h->d_vhdr = (CmxVerifyHdr*)a;
+    h->d_vseg = (unsigned long long*)b;
+  }
+  h->verify = on != 0;
+  return 0;
+}
+int cmx_mixnet_verify_on(cmx_mixnet_t* h) { return h && h->verify ? 1 : 0; }
+// DEVICE address of the sticky verify record (8 words, as cmx_mixnet_verify_report returns them), for callers that copy it back in stream order
+const unsigned long long* cmx_mixnet_verify_record(cmx_mixnet_t* h) { return h && h->d_vhdr ? h->d_vhdr->cum : nullptr; }
+int cmx_mixnet_verify_report(cmx_mixnet_t* h, uint64_t out[8]) {
+  const int fail_value = 1;
+  if (!h || !out) { set_err("cmx_mixnet_verify_report: bad argument"); return 1; }
+  if (!h->d_vhdr) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipDeviceSynchronize());
+  unsigned long long r[8];
+  HIP_OK(hipMemcpy(r, h->d_vhdr->cum, sizeof r, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 8; ++i) out[i] = r[i];
+  return 0;
+}
+// Test hook: one perturbation for the next chunk (see include/cmix_amd.h)
+int cmx_mixnet_debug_verify_perturb(cmx_mixnet_t* h, int cls, uint64_t bit, uint64_t index, uint32_t xor_mask) {
+  if (!h) { set_err("cmx_mixnet_debug_verify_perturb: null handle"); return 1; }
+  if (!h->verify) { set_err("cmx_mixnet_debug_verify_perturb: verify mode is off"); return 1; }
+  if (!xor_mask) { set_err("cmx_mixnet_debug_verify_perturb: a zero mask changes nothing"); return 1; }
+  uint64_t lim = 0;
+  switch (cls) {
+    case CMX_VC_ROW: case CMX_VC_RING_WRITTEN: case CMX_VC_RING_READ: lim = CMX_IN0; break;
+    case CMX_VC_SEL: lim = CMX_MIXERS; break;
+    case CMX_VC_BIT: case CMX_VC_DECAY_GATHER: case CMX_VC_DECAY_TAIL_A: case CMX_VC_DECAY_TAIL_B: lim = 1; break;
+    case CMX_VC_SEGMENT: lim = CMX_IN0; if (bit >= (uint64_t)CMX_MIX0 * CMX_ROWS_PER_MIXER) { set_err("cmx_mixnet_debug_verify_perturb: no such layer-0 row"); return 1; } break;
+    default: set_err("cmx_mixnet_debug_verify_perturb: bad class"); return 1;
+  }
+  if (index >= lim) { set_err("cmx_mixnet_debug_verify_perturb: index out of range for the class"); return 1; }
+  if (cls == CMX_VC_BIT && (xor_mask & ~0xffu)) { set_err("cmx_mixnet_debug_verify_perturb: the coded bit is a byte"); return 1; }
+  h->pert.cls = cls; h->pert.bit = bit; h->pert.index = index; h->pert.mask = xor_mask;
   return 0;
 }
 // DEVICE address of MixState::error (set by a chunk kernel whose bounded in-launch wait ran out), for callers that copy it back in
@@ -521,6 +602,7 @@ int cmx_mixnet_run(cmx_mixnet_t* h, const float* d_probs, const uint32_t* d_sel,
 int cmx_mixnet_run_late(cmx_mixnet_t* h, void* box, const float* probs, const uint32_t* sel, size_t nbits, void* stream) {
   if (!h || !box) { set_err("cmx_mixnet_run_late: bad argument"); return 1; }
   if (h->tolerance) { set_err("cmx_mixnet_run_late: a decoder needs the strict kernel (the tolerance switch is set)"); return 1; }
+  if (h->verify) { set_err("cmx_mixnet_run_late: verify mode covers the compressor's kernel only"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { set_err("hipSetDevice failed"); return 1; }
   if (h->late_p_cap < nbits || h->decay_cap < nbits) { set_err("cmx_mixnet_run_late: call cmx_mixnet_late_prepare first (nothing may be allocated while the stream's kernels run)"); return 1; }
   // (debug: three chunk-sized areas of mixer outputs in rotation, like the pipeline's buffer sets)
@@ -531,6 +613,7 @@ int cmx_mixnet_run_late(cmx_mixnet_t* h, void* box, const float* probs, const ui
 // everything the decoder's form allocates, for chunks of up to nbits bits: before the first chunk's kernels are launched
 int cmx_mixnet_late_prepare(cmx_mixnet_t* h, size_t nbits) {
   if (!h || !nbits) { set_err("cmx_mixnet_late_prepare: bad argument"); return 1; }
+  if (h->verify) { set_err("cmx_mixnet_late_prepare: verify mode covers the compressor's kernel only"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { set_err("hipSetDevice failed"); return 1; }
   if (h->late_p_cap < nbits) {
     void* p = nullptr;
@@ -566,6 +649,19 @@ static int mixnet_run_impl(cmx_mixnet_t* h, const float* d_probs, const uint32_t
   // other stages' uploads of chunks further ahead: their kernels then start a mixing-network period late).
   if (ensure_decay(h, nbits)) return 1;
   if (!h->s_up) { if (cmx_make_stream(&h->s_up, 2)) return 1; h->own_up = true; }
+  const size_t vblocks = (nbits + CMX_VERIFY_BLOCK - 1) / CMX_VERIFY_BLOCK;
+  if (!box && h->verify) {
+    if (h->pert.cls && h->pert.cls != CMX_VC_SEGMENT && h->pert.bit >= nbits) { set_err("cmx_mixnet_run: the armed verify perturbation lies outside the chunk"); return 1; }
+    if (vblocks > h->vrec_blocks) {   // the consumed sums of a launch: grown when a longer chunk comes (after the launches that use the old area)
+      HIP_OK(hipStreamSynchronize(st));
+      if (h->d_vrec) { for (auto& a : h->allocs) if (a == h->d_vrec) a = nullptr; (void)hipFree(h->d_vrec); h->d_vrec = nullptr; }
+      const size_t nb = vblocks < 512 ? 512 : vblocks;
+      void* a = nullptr;
+      HIP_OK(hipMalloc(&a, nb * CMX_VERIFY_REC * 8));
+      h->allocs.push_back(a);
+      h->d_vrec = (unsigned long long*)a; h->vrec_blocks = nb;
+    }
+  }
   const int slot = (int)(h->runs++ % CMX_PIPELINE_SLOTS);
   if (h->decay_used[slot]) HIP_OK(hipEventSynchronize(h->ev_kdone[slot]));   // the kernel that read this slot (implies its copy)
   float* hd = h->h_decay + (size_t)slot * h->decay_cap;
@@ -587,7 +683,29 @@ static int mixnet_run_impl(cmx_mixnet_t* h, const float* d_probs, const uint32_t
   if (box && box->box)   // a decoder's chunk: the patient instantiation of the same roles
     hipLaunchKernelGGL(cmx_mixnet_spec_late_kernel, dim3(grid), dim3(CMX_SPEC_THREADS), CMX_SPEC_LDS_BYTES, st,
                        h->d_state, h->d_xfer, d_probs, d_sel, dd, (int)nbits, d_p_out, d_mix_out, kmode, *box);
-  else {
+  else if (h->verify) {   // the same roles folding what they load, then the recomputation from HBM behind it (cmx_verify.h)
+    HIP_OK(hipMemsetAsync(h->d_vhdr, 0, CMX_VERIFY_CLEAR_BYTES, st));
+    HIP_OK(hipMemsetAsync(h->d_vrec, 0, vblocks * CMX_VERIFY_REC * 8, st));
+    const auto p = h->pert;
+    h->pert.cls = 0;
+    // (test hook) the word an input perturbation XORs: it changes between the network kernel and the verify kernel, and back after it
+    void* pw = nullptr; int pbytes = 4;
+    if (p.cls == CMX_VC_ROW) pw = (void*)(d_probs + p.bit * CMX_IN0 + p.index);
+    else if (p.cls == CMX_VC_SEL) pw = (void*)(d_sel + p.bit * CMX_MIXERS + p.index);
+    else if (p.cls == CMX_VC_BIT) { pw = (void*)(d_bits + p.bit); pbytes = 1; }
+    else if (p.cls == CMX_VC_DECAY_GATHER || p.cls == CMX_VC_DECAY_TAIL_A || p.cls == CMX_VC_DECAY_TAIL_B) pw = (void*)(dd + p.bit);
+    if (p.cls == CMX_VC_SEGMENT)   // a stored weight word of layer-0 row p.bit (mixer * 10001 + row), before the kernel that may load it
+      hipLaunchKernelGGL(cmx_mixnet_verify_xor_kernel, dim3(1), dim3(64), 0, st, (void*)(h->h_state.rows0 + p.bit * CMX_ROW0_STRIDE + p.index), 4, p.mask);
+    const bool ring = p.cls == CMX_VC_RING_WRITTEN || p.cls == CMX_VC_RING_READ;
+    const CmxVerify V = {h->d_vrec, h->d_vseg, h->d_vhdr, ring ? (int)p.bit : -1, ring ? (int)p.index : 0, ring ? p.mask : 0u};
+    hipLaunchKernelGGL(cmx_mixnet_spec_verify_kernel, dim3(grid), dim3(CMX_SPEC_THREADS), CMX_SPEC_LDS_BYTES, st,
+                       h->d_state, h->d_xfer, d_probs, d_sel, d_bits, dd, (int)nbits, d_p_out, d_mix_out, kmode, V);
+    HIP_OK(hipGetLastError());
+    if (pw) hipLaunchKernelGGL(cmx_mixnet_verify_xor_kernel, dim3(1), dim3(64), 0, st, pw, pbytes, p.mask);
+    hipLaunchKernelGGL(cmx_mixnet_verify_kernel, dim3((unsigned)vblocks), dim3(256), 0, st, (const MixState*)h->d_state, d_probs, d_sel, d_bits, (const float*)dd, (int)nbits, V);
+    if (pw) hipLaunchKernelGGL(cmx_mixnet_verify_xor_kernel, dim3(1), dim3(64), 0, st, pw, pbytes, p.mask);
+    hipLaunchKernelGGL(cmx_mixnet_verify_fold_kernel, dim3(1), dim3(64), 0, st, h->d_vhdr, (unsigned long long)h->bits_done, (int)nbits);
+  } else {
     hipLaunchKernelGGL(h->jitter ? cmx_mixnet_spec_jitter_kernel : cmx_mixnet_spec_kernel, dim3(grid), dim3(CMX_SPEC_THREADS), CMX_SPEC_LDS_BYTES, st,
                        h->d_state, h->d_xfer, d_probs, d_sel, d_bits, dd, (int)nbits, d_p_out, d_mix_out, kmode);
   }
@@ -603,6 +721,7 @@ float cmx_mixnet_predict(cmx_mixnet_t* h, const float* probs, const uint32_t* se
   const float fail_value = -1.0f;
   if (!h) { set_err("cmx_mixnet_predict: null handle"); return -1.0f; }
   if (h->predicted) { set_err("cmx_mixnet_predict: called twice without perceive()"); return -1.0f; }
+  if (h->verify) { set_err("cmx_mixnet_predict: verify mode covers chunks only (the bit-synchronous kernel writes rows it does not digest)"); return -1.0f; }
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipMemcpy(h->d_sync_probs, probs, CMX_IN0 * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(h->d_sync_sel, sel, CMX_MIXERS * 4, hipMemcpyHostToDevice));
@@ -642,6 +761,7 @@ int cmx_mixnet_predict_async(cmx_mixnet_t* h, const float* d_probs, const uint32
   const int fail_value = 1;
   if (!h || !d_probs || !d_sel || !d_p) { set_err("cmx_mixnet_predict_async: bad argument"); return 1; }
   if (h->predicted) { set_err("cmx_mixnet_predict_async: called twice without perceive()"); return 1; }
+  if (h->verify) { set_err("cmx_mixnet_predict_async: verify mode covers chunks only"); return 1; }
   HIP_OK(hipSetDevice(h->device));
   hipLaunchKernelGGL(cmx_mixnet_kernel, dim3(1), dim3(CMX_MIXNET_THREADS), kLdsBytes, (hipStream_t)stream, h->d_state,
                      d_probs, d_sel, h->d_sync_bit, (const float*)(h->d_sync_bit + 4), 1, d_p, (float*)nullptr, 1);
@@ -715,6 +835,11 @@ int cmx_mixnet_sync(cmx_mixnet_t* h) {
   int err = 0;
   HIP_OK(hipMemcpy(&err, (char*)h->d_state + offsetof(MixState, error), 4, hipMemcpyDeviceToHost));
   if (err) { set_err("cmx_mixnet: a device-side wait timed out (kernel aborted); state is invalid"); return 1; }
+  if (h->d_vhdr) {
+    unsigned long long r[8];
+    HIP_OK(hipMemcpy(r, h->d_vhdr->cum, sizeof r, hipMemcpyDeviceToHost));
+    if (r[2]) { set_err("cmx_mixnet_sync: " + cmx_mixnet_verify_text(r)); return 1; }
+  }
   return 0;
 }
 

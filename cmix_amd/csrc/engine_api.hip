@@ -81,6 +81,7 @@ struct cmx_engine {
   uint8_t vocab[256];
   std::string dict;               // the hidden global `dictionary_path` (runner.cpp:17), read by the fxcm stage
   bool has_dict = false;
+  bool verify = false;            // cmx_set_verify: the look-ahead pipeline's mixing network runs in verify mode
   int mode = 0;                   // 0 undecided, 1 per-bit stages built (columns from the caller), 2 look-ahead pipeline built, 3 the decoder's pipeline (late-bit protocol)
   LookAhead* la = nullptr;
   cmx_pipeline_t* late = nullptr; // mode 3: every model family on the device, bits arriving one at a time (cmx_pipeline_late_*)
@@ -317,7 +318,7 @@ int ensure_lookahead(cmx_engine* h) {
   h->la = la;
   la->pipe = cmx_pipeline_create(h->vocab, h->device, kLaChunk);
   bool ok = la->pipe && cmx_pipeline_enable_fxcm(la->pipe, h->has_dict ? h->dict.c_str() : nullptr) == 0 &&
-            cmx_pipeline_enable_paq8(la->pipe) == 0;
+            cmx_pipeline_enable_paq8(la->pipe) == 0 && (!h->verify || cmx_pipeline_set_verify(la->pipe, 1) == 0);
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
   const size_t T = 8 * kLaChunk;
   for (size_t i = 0; ok && i < kLaSlots; ++i) {
@@ -629,6 +630,19 @@ int cmx_decode_stream(cmx_t* h, const uint8_t* code, size_t code_len, uint8_t* o
   }
   cmx_decoder_destroy(d);
   return rc;
+}
+
+// verify mode of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input
+int cmx_set_verify(cmx_t* h, int on) {
+  if (!h) { cmx_set_err("cmx_set_verify: null handle"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_verify: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  h->verify = on != 0;
+  return 0;
+}
+int cmx_verify_report(cmx_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_verify_report: bad argument"); return 1; }
+  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing verified: not a compressor's handle, or nothing staged yet)
+  return cmx_pipeline_verify_report(h->la->pipe, out);
 }
 
 // 0 undecided, 1 per-bit stages, 2 look-ahead pipeline; in mode 2 *chunks_in_flight (may be NULL) = submitted - used up

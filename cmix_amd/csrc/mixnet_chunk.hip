@@ -18,6 +18,7 @@
 // Every spin is bounded; a timeout sets S->error and unwinds all roles.
 #include "mixnet_dev.h"
 #include "cmx_late.h"
+#include "cmx_verify.h"
 
 namespace {
 
@@ -90,6 +91,21 @@ template <bool JIT> __device__ __forceinline__ void jitter_stall(int jit, int t,
     const int n = (int)((h >> 3) & 31u);
     for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
   }
+}
+
+// Verify mode (cmx_mixnet_set_verify; the VER instantiation, cmx_mixnet_spec_verify_kernel): every role folds the words it loaded into block sums
+// (cmx_verify.h) in registers and stores them, one wave per word, into the launch's record; the helpers keep a digest of every layer-0 row segment they
+// store and check it when they load the segment again. Nothing of it changes what a role computes or when it waits. Unused in the other instantiations.
+// (CmxVerify, cmx_verify.h: what the VER instantiation is launched with)
+// sum over the wavefront, in every lane (block ends only)
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ void verify_flag(const CmxVerify& V, unsigned long long key) {   // one mismatch (one lane)
+  atomicAdd(&V.hdr->launch_count, 1ull);
+  atomicMax(&V.hdr->launch_first, ~key);
 }
 
 // All inter-wave traffic of this kernel goes through LDS, so its synchronisation only has to
@@ -277,7 +293,8 @@ struct SseInterp {  // SSEi<7>::SSE_Pred / SSE_Update on a cell held in register
   }
 };
 
-template <bool LATE, bool JIT = false> __device__ void tail_a_role(MixState* S, const Lds& L, const float* decay1, int nbits, float* mix_out, int lane, bool prof_on) {
+template <bool LATE, bool JIT = false, bool VER = false> __device__ void tail_a_role(MixState* S, const Lds& L, const float* decay1, int nbits, float* mix_out, int lane, bool prof_on,
+                                                                     const CmxVerify& V) {
   uint64_t tprev = __builtin_readcyclecounter();
   uint64_t pacc[6] = {0, 0, 0, 0, 0, 0};
 #define TPROF(k) do { if (prof_on) { uint64_t now_ = __builtin_readcyclecounter(); pacc[k - 6] += now_ - tprev; tprev = now_; } } while (0)
@@ -299,6 +316,7 @@ template <bool LATE, bool JIT = false> __device__ void tail_a_role(MixState* S, 
     for (int i = 0; i < 13; ++i) gstore4_async(row1 + 4 * i, *reinterpret_cast<const float4*>(w1 + 4 * i));
     asm volatile("global_store_dwordx2 %0, %1, off\n\ts_nop 0" :: "v"(rsp1), "v"(rs1) : "memory");
   };
+  unsigned long long vdec = 0;   // VER: the decay words of the block in progress (wave-uniform)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   for (int t = 0; t < nbits; ++t) {
     TPROF(11);
@@ -307,7 +325,9 @@ template <bool LATE, bool JIT = false> __device__ void tail_a_role(MixState* S, 
     const BitRec* rec = L.rec + (t % L.rr);
     const uint32_t newrow = rec->rowidx[CMX_MIX0 + kk];
     const uint32_t row2 = rec->rowidx[CMX_MIXERS - 1];
-    const double d1 = (double)as_global(decay1)[t];
+    const float d1f = as_global(decay1)[t];
+    if constexpr (VER) vdec += cmx_vmix(CMX_VC_DECAY_GATHER, (uint32_t)t, 0, __float_as_uint(d1f));   // (mix class of CMX_VC_DECAY_TAIL_A)
+    const double d1 = (double)d1f;
     if (is1 && newrow != cur_row) {
       if (cur_row != 0xffffffffu) store_row1();
       cur_row = newrow;
@@ -402,6 +422,12 @@ template <bool LATE, bool JIT = false> __device__ void tail_a_role(MixState* S, 
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     TPROF(10);
+    if constexpr (VER) {
+      if ((t + 1) % CMX_VERIFY_BLOCK == 0 || t + 1 == nbits) {
+        if (lane == 0) as_global(V.rec)[(size_t)(t / CMX_VERIFY_BLOCK) * CMX_VERIFY_REC + CMX_VR_DECAY + 1] = vdec;
+        vdec = 0;
+      }
+    }
   }
   if (prof_on && lane == 0) {
 #pragma unroll
@@ -414,7 +440,8 @@ template <bool LATE, bool JIT = false> __device__ void tail_a_role(MixState* S, 
   }
 }
 
-template <bool LATE, bool JIT = false> __device__ void tail_b_role(MixState* S, const Lds& L, const float* decay1, int nbits, float* p_out, float* mix_out, int lane, bool prof_on) {
+template <bool LATE, bool JIT = false, bool VER = false> __device__ void tail_b_role(MixState* S, const Lds& L, const float* decay1, int nbits, float* p_out, float* mix_out, int lane,
+                                                                     bool prof_on, const CmxVerify& V) {
   uint64_t tprev = __builtin_readcyclecounter();
   uint64_t pacc[3] = {0, 0, 0};
 #define TPROF(k) do { if (prof_on) { uint64_t now_ = __builtin_readcyclecounter(); pacc[k] += now_ - tprev; tprev = now_; } } while (0)
@@ -435,9 +462,12 @@ template <bool LATE, bool JIT = false> __device__ void tail_b_role(MixState* S, 
   uint64_t rs2 = 0, mx2 = S->max_steps[CMX_MIXERS - 1];
   unsigned sj = S->sse_j, spc = S->sse_pc, sffl = S->sse_ffl;
   uint64_t steps_done = 0;
+  unsigned long long vdec = 0;   // VER: the decay words of the block in progress (wave-uniform)
   for (int t = 0; t < nbits; ++t) {
     jitter_stall<JIT>(L.jit, t, 13);
-    const double d1 = (double)as_global(decay1)[t];
+    const float d1f = as_global(decay1)[t];
+    if constexpr (VER) vdec += cmx_vmix(CMX_VC_DECAY_GATHER, (uint32_t)t, 0, __float_as_uint(d1f));   // (mix class of CMX_VC_DECAY_TAIL_B)
+    const double d1 = (double)d1f;
     // SSE contexts for a = 0..2 / b = 0..3 (sse.cpp:248-262): lane i pulls candidate cell i towards the caches (see the tail's comment above)
     if (k < 13) {
       const unsigned j_ = bcast_u(sj), pc_ = bcast_u(spc), ffl_ = bcast_u(sffl);
@@ -559,6 +589,12 @@ template <bool LATE, bool JIT = false> __device__ void tail_b_role(MixState* S, 
     __builtin_amdgcn_wave_barrier();
     st_rel(&L.ctl->b_done, t + 1);
     TPROF(2);
+    if constexpr (VER) {
+      if ((t + 1) % CMX_VERIFY_BLOCK == 0 || t + 1 == nbits) {
+        if (lane == 0) as_global(V.rec)[(size_t)(t / CMX_VERIFY_BLOCK) * CMX_VERIFY_REC + CMX_VR_DECAY + 2] = vdec;
+        vdec = 0;
+      }
+    }
   }
   if (prof_on && lane == 0) {
 #pragma unroll
@@ -638,8 +674,8 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
 }
 
-template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, SpecXfer* X, HelperLds* H, int nbits, int m, int w, int lane, bool tol, CmxLateBox* LB, bool local, int jit,
-                                                                  const CmxLate& late, const float* probs) {
+template <bool LATE, bool JIT = false, bool VER = false> __device__ void helper_role(MixState* S, SpecXfer* X, HelperLds* H, int nbits, int m, int w, int lane, bool tol, CmxLateBox* LB,
+                                                                  bool local, int jit, const CmxLate& late, const float* probs, const CmxVerify& V) {
   const gptr<float> rows0 = as_global(S->rows0);
   const gptr<const float> lut = as_global(S->logit_lut);
   // four waves cut the 2078-term chain: 4 x 512 (+ 30) terms (other cuts, candidate counts and re-run forms were measured and are slower:
@@ -660,6 +696,25 @@ template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, 
   // has a wait for the main workgroup run out? a compressor's: by spin count; a decoder's (the wait then includes the host): by its box
   auto spun_out = [&](unsigned spins) { return LATE ? late_expired(LB, late_t0) : spins > SPEC_SPIN; };
   auto give_up = [&]() { lds_publish_store(&H->abort, 1); __hip_atomic_store(&X->fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  // VER: digest of this wave's segment of a row (words [0, 2078) only), in every lane; segt = the row's number in the table of layer-0 rows
+  auto seg_digest = [&](const float* v, uint32_t segt) -> unsigned long long {
+    unsigned long long d = 0;
+#pragma unroll
+    for (int k = 0; k < KS; ++k) d += cmx_vmix(CMX_VC_SEGMENT, segt, (uint32_t)(base + 64 * k + lane), __float_as_uint(v[k]));
+    if (tailk) d += cmx_vmix(CMX_VC_SEGMENT, segt, (uint32_t)(base + SEGN + lane), __float_as_uint(v[KS]));
+    return wave_sum_u64(d);
+  };
+  unsigned long long vring = 0;   // VER: the ring words of the block in progress (this lane's)
+  float Wev[KS + 1];              // VER: the row segment stored last, its digest is stored off the bit's critical path (seg_store)
+  uint32_t ev_segt = 0; bool ev_pend = false;
+  auto seg_store = [&]() {
+    if constexpr (VER) {
+      if (!ev_pend) return;
+      ev_pend = false;
+      const unsigned long long d = seg_digest(Wev, ev_segt);
+      if (lane == 0) as_global(V.seg)[(size_t)ev_segt * CMX_VERIFY_SEGS + w] = d;   // behind the segment's own stores (same wave, in order)
+    }
+  };
   // fetch the inputs of bit t (this wave's slice) and, if its selector changes, the incoming row
   auto fetch = [&](int t) -> bool {
     unsigned spins = 0;
@@ -678,6 +733,13 @@ template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, 
 #pragma unroll
       for (int k = 0; k < KS; ++k) Wn[k] = rows0[nb + 64 * k + lane];
       Wn[KS] = tailk ? rows0[nb + SEGN + lane] : 0.0f;
+      if constexpr (VER) {   // the segment against the digest stored with it (0: never stored by a verified launch)
+        const uint32_t segt = (nb - (uint32_t)base) / CMX_ROW0_STRIDE;
+        const unsigned long long want = as_global(V.seg)[(size_t)segt * CMX_VERIFY_SEGS + w];
+        const unsigned long long got = seg_digest(Wn, segt);
+        if (lane == 0 && want != 0 && want != got)
+          verify_flag(V, cmx_vkey((uint32_t)t / CMX_VERIFY_BLOCK, CMX_VC_SEGMENT, (uint32_t)m, segt - (uint32_t)m * CMX_ROWS_PER_MIXER, (uint32_t)w));
+      }
     }
     if (LATE) {
       // round 6: this wave's slice of the bit's inputs straight from the producers' row (uncached device memory), as soon as the stages that write its columns have
@@ -708,6 +770,16 @@ template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, 
 #pragma unroll
       for (int k = 0; k < KS; ++k) xc[k] = ld_f32(gx + 64 * k + lane);
       xc[KS] = tailk ? ld_f32(gx + SEGN + lane) : 0.0f;
+      if constexpr (VER) {   // the slice as loaded, into helper m's ring sums (mix class of CMX_VC_RING_READ)
+#pragma unroll
+        for (int k = 0; k < KS; ++k) vring += cmx_vmix(CMX_VC_RING_WRITTEN, (uint32_t)t, (uint32_t)(base + 64 * k + lane), __float_as_uint(xc[k]));
+        if (tailk) vring += cmx_vmix(CMX_VC_RING_WRITTEN, (uint32_t)t, (uint32_t)(base + SEGN + lane), __float_as_uint(xc[KS]));
+        if ((t + 1) % CMX_VERIFY_BLOCK == 0 || t + 1 == nbits) {
+          const unsigned long long v = wave_sum_u64(vring);
+          if (lane == 0) as_global(V.rec)[(size_t)(t / CMX_VERIFY_BLOCK) * CMX_VERIFY_REC + CMX_VR_RINGR + 4 * m + w] = v;
+          vring = 0;
+        }
+      }
     }
     return true;
   };
@@ -742,6 +814,11 @@ template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, 
 #pragma unroll
         for (int k = 0; k < KS; ++k) rows0[cur_base + 64 * k + lane] = W[k];
         if (tailk) rows0[cur_base + SEGN + lane] = W[KS];
+        if constexpr (VER) {
+#pragma unroll
+          for (int k = 0; k < KS + 1; ++k) Wev[k] = W[k];
+          ev_segt = (cur_base - (uint32_t)base) / CMX_ROW0_STRIDE; ev_pend = true;
+        }
       }
       if (live) {
         cur_base = f_base;
@@ -749,7 +826,7 @@ template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, 
         for (int k = 0; k < KS + 1; ++k) W[k] = Wn[k];
       }
     }
-    if (!live) break;
+    if (!live) { seg_store(); break; }
     // ---- products of bit t (mixer.cpp:41: in[i] * w[i], rounded) -> LDS, f64 sum of the segment ----
     float* pr = H->prod[w];
     double ds = 0.0;
@@ -778,6 +855,7 @@ template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, 
         tot += ds;
         if (lane == 0) st_u64(&X->sum[m], ((unsigned long long)(unsigned)(t + 1) << 32) | (unsigned)__float_as_int((float)tot));
       }
+      seg_store();
       if (t + 1 < nbits && !fetch(t + 1)) return;
       continue;
     }
@@ -830,6 +908,7 @@ template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, 
     // ---- while the gather wave works: the inputs / incoming row of bit t+1 ----
     jitter_stall<JIT>(jit, t, 144 + 4 * m + w);
     if (LATE && !apply_u(t + 1)) return;     // (a decoder: u of THIS bit first -- it arrives with the bit, the next row much later)
+    seg_store();                              // (VER: before the next fetch, which may load the same segment back)
     if (t + 1 < nbits && !fetch(t + 1)) return;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -843,10 +922,12 @@ template <bool LATE, bool JIT = false> __device__ void helper_role(MixState* S, 
 // and two more for the row selection), more than a whole bit of the helpers. Only Mixer::GetContextData is stateful; the stretch of a
 // bit's inputs depends on nothing, so four stretch waves take the bits round robin (each bit still costs its ~12 k clocks, four
 // are in flight) and one select wave follows them in order.
-template <bool LATE, bool JIT = false> __device__ void stretch_role(MixState* S, const Lds& L, SpecXfer* X, const float* probs, const uint8_t* bits, int nbits, int sw, int lane) {
+template <bool LATE, bool JIT = false, bool VER = false> __device__ void stretch_role(MixState* S, const Lds& L, SpecXfer* X, const float* probs, const uint8_t* bits, int nbits, int sw,
+                                                                      int lane, const CmxVerify& V) {
   const gptr<const float> lut = as_global(S->logit_lut);
   const gptr<const float> gprobs = as_global(probs);
   const float smin = S->stretch_min, smax = S->stretch_max;
+  unsigned long long vrow = 0, vbit = 0, vring = 0;   // VER: this lane's sums of the block in progress (raw inputs, coded bit, stretched inputs stored)
   for (int t = sw; t < nbits; t += 4) {
     jitter_stall<JIT>(L.jit, t, 4 + sw);
     if (t >= L.lead && !wait_ge<LATE>(L.ctl, &L.ctl->consumed, 4 * (t - L.lead) + 1, true)) return;   // the gather wave has begun bit t - lead
@@ -877,7 +958,13 @@ template <bool LATE, bool JIT = false> __device__ void stretch_role(MixState* S,
         pv[r] = i < CMX_IN0 ? pr[i] : 0.5f;
       }
     }
+    if constexpr (VER) {
+#pragma unroll
+      for (int r = 0; r < 33; ++r)
+        if (r * 64 + lane < CMX_IN0) vrow += cmx_vmix(CMX_VC_ROW, (uint32_t)t, (uint32_t)(r * 64 + lane), __float_as_uint(pv[r]));
+    }
     const int bitv = LATE ? 0 : (int)bits[t];   // (late: not known yet; the waves that learn wait for it)
+    if constexpr (VER) { if (lane == 0) vbit += cmx_vmix(CMX_VC_BIT, (uint32_t)t, 0, (uint32_t)bitv); }
     const float lstm_raw = bcast_lane(pv[32], 29);   // probs[t][2077]
 #pragma unroll
     for (int r = 0; r < 33; ++r) {   // MixerInput::SetInput (mixer-input.cpp:11-15) + Sigmoid::Logit (sigmoid.cpp:12-17)
@@ -894,7 +981,15 @@ template <bool LATE, bool JIT = false> __device__ void stretch_role(MixState* S,
 #pragma unroll
       for (int r = 0; r < 33; ++r) {
         int i = r * 64 + lane;
-        if (i < CMX_IN0) __hip_atomic_store(gx + i, pv[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (VER) {
+          if (i < CMX_IN0) {
+            vring += cmx_vmix(CMX_VC_RING_WRITTEN, (uint32_t)t, (uint32_t)i, __float_as_uint(pv[r]));
+            const float sv = (t == V.pert_bit && i == V.pert_index) ? __uint_as_float(__float_as_uint(pv[r]) ^ V.pert_mask) : pv[r];   // (test hook)
+            __hip_atomic_store(gx + i, sv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        } else {
+          if (i < CMX_IN0) __hip_atomic_store(gx + i, pv[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
       }
     }
     const float ax0 = bcast_lane(pv[6], 49), ax1 = bcast_lane(pv[31], 40), ax2 = bcast_lane(pv[32], 29);   // columns 433, 2024, 2077
@@ -917,15 +1012,28 @@ template <bool LATE, bool JIT = false> __device__ void stretch_role(MixState* S,
     __builtin_amdgcn_wave_barrier();
     jitter_stall<JIT>(L.jit, t, 8 + sw);
     if (lane == 0) st_rel(&L.sdone[t % L.rr], t + 1);
+    if constexpr (VER) {   // this wave's last bit of the block: its three sums
+      if (t + 4 >= nbits || (t + 4) / CMX_VERIFY_BLOCK != t / CMX_VERIFY_BLOCK) {
+        const unsigned long long a = wave_sum_u64(vrow), b = wave_sum_u64(vbit), c = wave_sum_u64(vring);
+        if (lane == 0) {
+          const gptr<unsigned long long> rec = as_global(V.rec) + (size_t)(t / CMX_VERIFY_BLOCK) * CMX_VERIFY_REC;
+          rec[CMX_VR_ROW + sw] = a; rec[CMX_VR_BIT + sw] = b; rec[CMX_VR_RINGW + sw] = c;
+        }
+        vrow = vbit = vring = 0;
+      }
+    }
   }
 }
 
-template <bool LATE, bool JIT = false> __device__ void select_role(MixState* S, const Lds& L, SpecXfer* X, const uint32_t* sel, const float* probs, int nbits, int lane) {
+template <bool LATE, bool JIT = false, bool VER = false> __device__ void select_role(MixState* S, const Lds& L, SpecXfer* X, const uint32_t* sel, const float* probs, int nbits, int lane,
+                                                                     const CmxVerify& V) {
   const gptr<const uint32_t> gsel = as_global(sel);
   const gptr<const float> lut = as_global(S->logit_lut);
+  unsigned long long vsel = 0;   // VER: this lane's selector words of the block in progress
   for (int t = 0; t < nbits; ++t) {
     jitter_stall<JIT>(L.jit, t, 2);
     uint32_t key = (!LATE && lane < CMX_MIXERS) ? gsel[(size_t)t * CMX_MIXERS + lane] : 0;
+    if constexpr (VER) { if (lane < CMX_MIXERS) vsel += cmx_vmix(CMX_VC_SEL, (uint32_t)t, (uint32_t)lane, key); }
     BitRec* rec = L.rec + (t % L.rr);
     const BitRec* prev = L.rec + ((t + L.rr - 1) % L.rr);
     if (LATE) {
@@ -1003,6 +1111,13 @@ template <bool LATE, bool JIT = false> __device__ void select_role(MixState* S, 
     if (!LATE && lane == 0) __hip_atomic_store(&X->scout_epoch, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (a decoder: published above, ahead of the stretch wave)
     st_rel(&L.ctl->scout_epoch, t + 1);
     if (LATE && lane == 0) late_stamp(L.late, 5);   // inputs and rows published to the helpers
+    if constexpr (VER) {
+      if ((t + 1) % CMX_VERIFY_BLOCK == 0 || t + 1 == nbits) {
+        const unsigned long long v = wave_sum_u64(vsel);
+        if (lane == 0) as_global(V.rec)[(size_t)(t / CMX_VERIFY_BLOCK) * CMX_VERIFY_REC + CMX_VR_SEL] = v;
+        vsel = 0;
+      }
+    }
   }
 }
 
@@ -1010,8 +1125,8 @@ template <bool LATE, bool JIT = false> __device__ void select_role(MixState* S, 
 // The 26 ordered sums arrive from the helpers; what stays here is the serial rest of layer 0. Per-row state of lane m's current weight row
 // stays in registers while the selector does not change: the 0..25 extra weights (mixer.cpp:45-53), the row's step counter
 // (ContextData::steps) and the mixer's max_steps_. It is swapped only when the row changes.
-template <bool LATE, bool JIT = false> __device__ void gather_role(MixState* S, const Lds& L, SpecXfer* X, const float* decay1, int nbits,
-                            float* mix_out, bool prof_on, int lane, bool local) {
+template <bool LATE, bool JIT = false, bool VER = false> __device__ void gather_role(MixState* S, const Lds& L, SpecXfer* X, const float* decay1, int nbits,
+                            float* mix_out, bool prof_on, int lane, bool local, const CmxVerify& V) {
   const int m = lane;
   const bool is0 = m < CMX_MIX0;
   const float smin = S->stretch_min, smax = S->stretch_max;
@@ -1052,6 +1167,7 @@ template <bool LATE, bool JIT = false> __device__ void gather_role(MixState* S, 
   float d1n = 0.0f;
 #pragma unroll
   for (int i = 0; i < 7; ++i) ewn[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  unsigned long long vdec = 0;   // VER: the decay words of the block in progress (wave-uniform)
   for (int t = 0; t < nbits; ++t) {
     jitter_stall<JIT>(L.jit, t, 0);
     if (!wait_ge<LATE>(L.ctl, &L.ctl->scout_epoch, t + 1, false)) return;
@@ -1079,7 +1195,9 @@ template <bool LATE, bool JIT = false> __device__ void gather_role(MixState* S, 
       for (int i = 0; i < 28; ++i)
         if (i >= m) ew[i] = 0.0f;
     }
-    const double d1 = (double)(d1_t == t ? d1n : as_global(decay1)[t]);  // (float)(0.9/pow(1e-7*steps_+0.8,0.8)), host libm; fetched a bit ahead
+    const float d1f = d1_t == t ? d1n : as_global(decay1)[t];
+    if constexpr (VER) vdec += cmx_vmix(CMX_VC_DECAY_GATHER, (uint32_t)t, 0, __float_as_uint(d1f));
+    const double d1 = (double)d1f;  // (float)(0.9/pow(1e-7*steps_+0.8,0.8)), host libm; fetched a bit ahead
     const float decay = (float)(d1 * (1.5 - ((1.0 * (double)rsteps) / (double)mx)));   // mixer.cpp:58-60
     const float dlr = fmul(decay, lr);
     GPROF(1);
@@ -1170,6 +1288,12 @@ template <bool LATE, bool JIT = false> __device__ void gather_role(MixState* S, 
       pf_t = t + 1;
     }
     GPROF(5);
+    if constexpr (VER) {
+      if ((t + 1) % CMX_VERIFY_BLOCK == 0 || t + 1 == nbits) {
+        if (lane == 0) as_global(V.rec)[(size_t)(t / CMX_VERIFY_BLOCK) * CMX_VERIFY_REC + CMX_VR_DECAY] = vdec;
+        vdec = 0;
+      }
+    }
   }
   if (is0 && nbits > 0) {
     store_row_state();
@@ -1188,10 +1312,11 @@ template <bool LATE, bool JIT = false> __device__ void gather_role(MixState* S, 
 // LATE: a decoder's chunk (cmx_late.h) -- `bits` is unused, rows / selectors arrive as their stages count them, p goes to the box. A compile-time
 // switch: the compressor's kernel carries none of the decoder's state (125 VGPRs / 71 spilled SGPRs as before the decoder existed, against
 // 167 / 135 when the two forms shared one kernel body at run time; the measured time per bit is the same either way, 6.8 us in the pipeline).
-template <bool LATE, bool JIT = false> __device__ __forceinline__ void spec_kernel_body(
+template <bool LATE, bool JIT = false, bool VER = false> __device__ __forceinline__ void spec_kernel_body(
     MixState* __restrict__ S, SpecXfer* __restrict__ X, const float* __restrict__ probs, const uint32_t* __restrict__ sel,
     const uint8_t* __restrict__ bits, const float* __restrict__ decay1, int nbits,
-    float* __restrict__ p_out, float* __restrict__ mix_out, int mode, const CmxLate& box) {
+    float* __restrict__ p_out, float* __restrict__ mix_out, int mode, const CmxLate& box, const CmxVerify& V = CmxVerify()) {
+  static_assert(!(LATE && VER), "verify mode covers the compressor's form only");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -1242,7 +1367,7 @@ template <bool LATE, bool JIT = false> __device__ __forceinline__ void spec_kern
     __syncthreads();
     CmxLateBox* const lb = LATE ? box.box : nullptr;
     const bool tol = !LATE && (mode & 0x1000) != 0;   // a decoder needs the exact sums: the late form has no tolerance mode
-    if (wave < 4) helper_role<LATE, JIT>(S, X, H, nbits, role - 1, wave, lane, tol, lb, local, JIT ? ((mode >> 26) & 15) | 16 : 0, box, probs);
+    if (wave < 4) helper_role<LATE, JIT, VER>(S, X, H, nbits, role - 1, wave, lane, tol, lb, local, JIT ? ((mode >> 26) & 15) | 16 : 0, box, probs, V);
     return;
   }
   Lds L;
@@ -1272,11 +1397,11 @@ template <bool LATE, bool JIT = false> __device__ __forceinline__ void spec_kern
   if (LATE && tid == 0) { L.ctl->late_lo = (unsigned)(unsigned long long)box.box; L.ctl->late_hi = (unsigned)((unsigned long long)box.box >> 32); }   // (0 otherwise: cleared above)
   __syncthreads();
   const bool prof = (mode & 4) != 0;
-  if (wave == 0) gather_role<LATE, JIT>(S, L, X, decay1, nbits, mix_out, prof, lane, local);
-  else if (wave == 1) tail_a_role<LATE, JIT>(S, L, decay1, nbits, mix_out, lane, prof && ((mode >> 4) & 4) != 0);
-  else if (wave == 3) tail_b_role<LATE, JIT>(S, L, decay1, nbits, p_out, mix_out, lane, prof && ((mode >> 4) & 4) != 0);
-  else if (wave == 2) select_role<LATE, JIT>(S, L, X, sel, probs, nbits, lane);
-  else if (wave >= 4) stretch_role<LATE, JIT>(S, L, X, probs, bits, nbits, wave - 4, lane);
+  if (wave == 0) gather_role<LATE, JIT, VER>(S, L, X, decay1, nbits, mix_out, prof, lane, local, V);
+  else if (wave == 1) tail_a_role<LATE, JIT, VER>(S, L, decay1, nbits, mix_out, lane, prof && ((mode >> 4) & 4) != 0, V);
+  else if (wave == 3) tail_b_role<LATE, JIT, VER>(S, L, decay1, nbits, p_out, mix_out, lane, prof && ((mode >> 4) & 4) != 0, V);
+  else if (wave == 2) select_role<LATE, JIT, VER>(S, L, X, sel, probs, nbits, lane, V);
+  else if (wave >= 4) stretch_role<LATE, JIT, VER>(S, L, X, probs, bits, nbits, wave - 4, lane, V);
   __syncthreads();
   if (tid == 0 && (L.ctl->abort || ld_u32(&X->fail))) S->error = 1;
 }
@@ -1301,4 +1426,110 @@ extern "C" __global__ __launch_bounds__(CMX_SPEC_THREADS) void cmx_mixnet_spec_l
     MixState* __restrict__ S, SpecXfer* __restrict__ X, const float* __restrict__ probs, const uint32_t* __restrict__ sel,
     const float* __restrict__ decay1, int nbits, float* __restrict__ p_out, float* __restrict__ mix_out, int mode, CmxLate box) {
   spec_kernel_body<true>(S, X, probs, sel, nullptr, decay1, nbits, p_out, mix_out, mode, box);
+}
+
+// ==================================================================================================================================
+// Verify mode (cmx_mixnet_set_verify): the compressor's kernel with every role folding what it loaded (VER), then, behind it on the
+// same stream, cmx_mixnet_verify_kernel recomputes every block sum from HBM and cmx_mixnet_verify_fold_kernel adds the launch to the handle's sticky
+// record. A mismatch is counted and recorded; it changes no control flow and no result.
+extern "C" __global__ __launch_bounds__(CMX_SPEC_THREADS) void cmx_mixnet_spec_verify_kernel(
+    MixState* __restrict__ S, SpecXfer* __restrict__ X, const float* __restrict__ probs, const uint32_t* __restrict__ sel,
+    const uint8_t* __restrict__ bits, const float* __restrict__ decay1, int nbits,
+    float* __restrict__ p_out, float* __restrict__ mix_out, int mode, CmxVerify V) {
+  spec_kernel_body<false, false, true>(S, X, probs, sel, bits, decay1, nbits, p_out, mix_out, mode, CmxLate(), V);
+}
+
+// One workgroup per block of CMX_VERIFY_BLOCK bits: the block's sums of every class from the buffers in HBM (the stretched inputs through the stretch
+// wave's arithmetic), against the sums the roles folded. Bandwidth-bound: it reads the block's 64 x 2078 inputs once.
+constexpr int VERIFY_THREADS = 256;
+extern "C" __global__ __launch_bounds__(VERIFY_THREADS) void cmx_mixnet_verify_kernel(const MixState* __restrict__ S, const float* __restrict__ probs,
+                                                                                     const uint32_t* __restrict__ sel, const uint8_t* __restrict__ bits,
+                                                                                     const float* __restrict__ decay1, int nbits, CmxVerify V) {
+  const int blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t0 = blk * CMX_VERIFY_BLOCK;
+  const int tn = nbits - t0 < CMX_VERIFY_BLOCK ? nbits - t0 : CMX_VERIFY_BLOCK;
+  const gptr<const float> lut = as_global(S->logit_lut);
+  unsigned long long e[5] = {0, 0, 0, 0, 0};   // ROW, RING (stretched), BIT, SEL, DECAY
+  for (int j = tid; j < tn * CMX_IN0; j += VERIFY_THREADS) {
+    const int t = t0 + j / CMX_IN0, i = j % CMX_IN0;
+    const float pv = as_global(probs)[(size_t)t * CMX_IN0 + i];
+    e[0] += cmx_vmix(CMX_VC_ROW, (uint32_t)t, (uint32_t)i, __float_as_uint(pv));
+    float p = pv;   // MixerInput::SetInput + Sigmoid::Logit, as stretch_role
+    if (p < 1.0e-4f) p = 1.0e-4f;
+    else if (p > 1 - 1.0e-4f) p = 1 - 1.0e-4f;
+    int idx = (int)(p * 100001.0f);
+    if (idx >= 100001) idx = 100000;
+    else if (idx < 0) idx = 0;
+    e[1] += cmx_vmix(CMX_VC_RING_WRITTEN, (uint32_t)t, (uint32_t)i, __float_as_uint(lut[idx]));
+  }
+  for (int j = tid; j < tn * CMX_MIXERS; j += VERIFY_THREADS) {
+    const int t = t0 + j / CMX_MIXERS, i = j % CMX_MIXERS;
+    e[3] += cmx_vmix(CMX_VC_SEL, (uint32_t)t, (uint32_t)i, as_global(sel)[(size_t)t * CMX_MIXERS + i]);
+  }
+  if (tid < tn) {
+    e[2] = cmx_vmix(CMX_VC_BIT, (uint32_t)(t0 + tid), 0, (uint32_t)as_global(bits)[t0 + tid]);
+    e[4] = cmx_vmix(CMX_VC_DECAY_GATHER, (uint32_t)(t0 + tid), 0, __float_as_uint(as_global(decay1)[t0 + tid]));
+  }
+  __shared__ unsigned long long part[VERIFY_THREADS / 64][5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const unsigned long long v = wave_sum_u64(e[k]);
+    if (lane == 0) part[wave][k] = v;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  unsigned long long x[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) x[k] = part[0][k] + part[1][k] + part[2][k] + part[3][k];
+  const gptr<const unsigned long long> rec = as_global((const unsigned long long*)V.rec) + (size_t)blk * CMX_VERIFY_REC;
+  unsigned long long n = 0, first = ~0ull;
+  auto check = [&](unsigned long long got, unsigned long long want, uint32_t cls, uint32_t m) {
+    if (got == want) return;
+    ++n;
+    const unsigned long long k = cmx_vkey((uint32_t)blk, cls, m, 0, 0);
+    if (k < first) first = k;
+  };
+  check(rec[CMX_VR_ROW] + rec[CMX_VR_ROW + 1] + rec[CMX_VR_ROW + 2] + rec[CMX_VR_ROW + 3], x[0], CMX_VC_ROW, 0);
+  check(rec[CMX_VR_BIT] + rec[CMX_VR_BIT + 1] + rec[CMX_VR_BIT + 2] + rec[CMX_VR_BIT + 3], x[2], CMX_VC_BIT, 0);
+  check(rec[CMX_VR_SEL], x[3], CMX_VC_SEL, 0);
+  check(rec[CMX_VR_DECAY], x[4], CMX_VC_DECAY_GATHER, 0);
+  check(rec[CMX_VR_DECAY + 1], x[4], CMX_VC_DECAY_TAIL_A, 0);
+  check(rec[CMX_VR_DECAY + 2], x[4], CMX_VC_DECAY_TAIL_B, 0);
+  check(rec[CMX_VR_RINGW] + rec[CMX_VR_RINGW + 1] + rec[CMX_VR_RINGW + 2] + rec[CMX_VR_RINGW + 3], x[1], CMX_VC_RING_WRITTEN, 0);
+  for (int m = 0; m < CMX_MIX0; ++m) {
+    const int b = CMX_VR_RINGR + 4 * m;
+    check(rec[b] + rec[b + 1] + rec[b + 2] + rec[b + 3], x[1], CMX_VC_RING_READ, (uint32_t)m);
+  }
+  if (n) {
+    atomicAdd(&V.hdr->launch_count, n);
+    atomicMax(&V.hdr->launch_first, ~first);
+  }
+}
+
+// The launch into the handle's sticky record (CmxVerifyHdr::cum, what cmx_mixnet_verify_report returns); bit0 = the stream bit of the launch's bit 0.
+extern "C" __global__ void cmx_mixnet_verify_fold_kernel(CmxVerifyHdr* H, unsigned long long bit0, int nbits) {
+  if (threadIdx.x != 0) return;
+  const gptr<unsigned long long> cum = as_global(H->cum);
+  const unsigned long long n = __hip_atomic_load(&H->launch_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned long long f = ~__hip_atomic_load(&H->launch_first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  cum[0] = cum[0] + 1;
+  cum[1] = cum[1] + (unsigned long long)nbits;
+  if (n) {
+    if (cum[2] == 0) {
+      const unsigned cls = (unsigned)(f >> 36) & 15u;
+      cum[3] = cls;
+      cum[4] = bit0 + (f >> 40) * CMX_VERIFY_BLOCK;
+      cum[5] = cls == CMX_VC_RING_READ || cls == CMX_VC_SEGMENT ? (f >> 31) & 31u : ~0ull;
+      cum[6] = cls == CMX_VC_SEGMENT ? (f >> 17) & 0x3fffu : ~0ull;
+      cum[7] = cls == CMX_VC_SEGMENT ? (f >> 15) & 3u : ~0ull;
+    }
+    cum[2] = cum[2] + n;
+  }
+}
+
+// Test hook (cmx_mixnet_debug_verify_perturb): XOR one word (bytes == 4) or one byte (bytes == 1) of a buffer in HBM.
+extern "C" __global__ void cmx_mixnet_verify_xor_kernel(void* p, int bytes, unsigned mask) {
+  if (threadIdx.x != 0) return;
+  if (bytes == 1) { uint8_t* q = (uint8_t*)p; *q = (uint8_t)(*q ^ (uint8_t)mask); }
+  else { unsigned* q = (unsigned*)p; *q = *q ^ mask; }
 }

@@ -31,6 +31,7 @@
 extern "C" int cmx_p8stage_streams(cmx_p8stage_t* h, hipStream_t* out, int cap);   // p8stage.hip: the role streams
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
+std::string cmx_mixnet_verify_text(const unsigned long long r[8]);  // cmx_api.hip: a verify record in words
 static double late_now();   // ms on the steady clock (defined with the late-bit pipeline below)
 
 // ---- construction ahead of time ------------------------------------------------------------------------------
@@ -113,6 +114,7 @@ struct Slot {
   float* d_hint = nullptr;      // [8 max + 1] f32 LSTM bit predictions, then [8 max + 1] i32 `ex` (look-ahead hybrid)
   float* h_hint = nullptr;      // pinned mirror
   unsigned* h_fail = nullptr;   // pinned [4]: the LSTM's / fxcm's / mixing network's sticky hand-off flags as they stood behind this chunk's kernels
+  unsigned long long* h_vrec = nullptr;   // pinned [8]: the mixing network's verify record as it stood behind this chunk's kernels (verify mode)
   size_t n = 0;                 // bytes of the chunk in this slot
   float* d_layer0 = nullptr;    // the caller's layer-0 rows of that chunk
   float* d_p = nullptr;         // the caller's p[] buffer of that chunk (cmx_pipeline_fetch)
@@ -304,6 +306,7 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
     if (s.d_hint) (void)hipFree(s.d_hint);
     if (s.h_hint) (void)hipHostFree(s.h_hint);
     if (s.h_fail) (void)hipHostFree(s.h_fail);
+    if (s.h_vrec) (void)hipHostFree(s.h_vrec);
     if (s.d_fx_pr) (void)hipFree(s.d_fx_pr);
     if (s.d_fx_ex) (void)hipFree(s.d_fx_ex);
     for (hipEvent_t e : {s.ev_fxin, s.ev_fx0, s.ev_fx1, s.ev_p80, s.ev_p81})
@@ -369,7 +372,8 @@ cmx_pipeline_t* cmx_pipeline_create(const uint8_t vocab[256], int device, size_t
     ok = ok && hipMalloc((void**)&s.d_hint, 2 * (8 * n + 1) * 4) == hipSuccess;
     ok = ok && hipHostMalloc((void**)&s.h_hint, 2 * (8 * n + 1) * 4, hipHostMallocDefault) == hipSuccess;
     ok = ok && hipHostMalloc((void**)&s.h_fail, 16, hipHostMallocDefault) == hipSuccess;
-    if (ok) s.h_fail[0] = s.h_fail[1] = s.h_fail[2] = s.h_fail[3] = 0;
+    ok = ok && hipHostMalloc((void**)&s.h_vrec, 64, hipHostMallocDefault) == hipSuccess;
+    if (ok) { s.h_fail[0] = s.h_fail[1] = s.h_fail[2] = s.h_fail[3] = 0; memset(s.h_vrec, 0, 64); }
     for (hipEvent_t* e : {&s.ev_in, &s.ev_ctx0, &s.ev_ctx1, &s.ev_lstm0, &s.ev_lstm1, &s.ev_mix0, &s.ev_mix1, &s.ev_cols})
       ok = ok && hipEventCreate(e) == hipSuccess;
   }
@@ -466,6 +470,17 @@ int cmx_pipeline_set_tolerance(cmx_pipeline_t* h, int on) {
   if (cmx_lstm_set_tolerance(h->lstm, on)) { (void)cmx_mixnet_set_tolerance(h->mix, was == 1); return 1; }
   h->lstm_tolerance = on != 0;
   return 0;
+}
+// verify mode of the mixing network (cmx_mixnet_set_verify), before the first chunk; cmx_pipeline_wait then fails the chunk in which a mismatch showed
+int cmx_pipeline_set_verify(cmx_pipeline_t* h, int on) {
+  if (!h) { cmx_set_err("cmx_pipeline_set_verify: null handle"); return 1; }
+  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_verify: only before the first chunk"); return 1; }
+  if (on && h->lstm_tolerance) { cmx_set_err("cmx_pipeline_set_verify: the tolerance switch is set (verify mode checks the strict kernel)"); return 1; }
+  return cmx_mixnet_set_verify(h->mix, on);
+}
+int cmx_pipeline_verify_report(cmx_pipeline_t* h, uint64_t out[8]) {
+  if (!h) { cmx_set_err("cmx_pipeline_verify_report: null handle"); return 1; }
+  return cmx_mixnet_verify_report(h->mix, out);
 }
 // 0 strict, 1 tolerance: not strict as soon as EITHER the mixing network or the LSTM computes in its tolerance form
 int cmx_pipeline_stage_overlap(cmx_pipeline_t* h) { return h ? h->overlap : -1; }
@@ -640,6 +655,7 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
   // the kernel's sticky time-out word, in stream order behind it: cmx_pipeline_wait looks at it per chunk (a look-ahead coder never
   // calls cmx_pipeline_sync, the only other place where it is read)
   (void)hipMemcpyAsync(&s.h_fail[2], cmx_mixnet_error_flag(h->mix), 4, hipMemcpyDeviceToHost, h->s_mix);
+  if (cmx_mixnet_verify_on(h->mix)) (void)hipMemcpyAsync(s.h_vrec, cmx_mixnet_verify_record(h->mix), 64, hipMemcpyDeviceToHost, h->s_mix);   // (the same for verify mode's record)
   (void)hipEventRecord(s.ev_mix1, h->s_mix);
   s.d_p = d_p_out;
   h->host_ms[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fin).count();
@@ -734,6 +750,11 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
   if (s.h_fail[0] || s.h_fail[1] || s.h_fail[2] || p8fail) {
     cmx_set_err(std::string("cmx_pipeline_wait: an in-launch hand-off of the ") + (s.h_fail[0] ? "LSTM" : s.h_fail[1] ? "fxcm" : s.h_fail[2] ? "mixing network" : "paq8 mixer") +
                 " kernels timed out (workgroups not co-resident?): the stream's output is void from chunk " + std::to_string(index) + " on");
+    h->failed = true;
+    return 1;
+  }
+  if (s.h_vrec[2]) {   // verify mode: a word the mixing network consumed in this chunk or an earlier one differs from its source (the record is sticky)
+    cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + cmx_mixnet_verify_text(s.h_vrec));
     h->failed = true;
     return 1;
   }

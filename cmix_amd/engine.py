@@ -156,6 +156,13 @@ def lib():
         L.cmx_hw_queues.argtypes = [C.c_int]
         L.cmx_mixnet_set_tolerance.argtypes = [C.c_void_p, C.c_int]
         L.cmx_mixnet_mode.argtypes = [C.c_void_p]
+        L.cmx_mixnet_set_verify.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_mixnet_verify_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_mixnet_debug_verify_perturb.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]
+        L.cmx_pipeline_set_verify.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_pipeline_verify_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_set_verify.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_verify_report.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_pipeline_late_start.argtypes = [C.c_void_p, C.c_int]
         L.cmx_pipeline_late_predict.restype = C.c_float
         L.cmx_pipeline_late_predict.argtypes = [C.c_void_p]
@@ -181,6 +188,23 @@ def device_count():
     return lib().cmx_device_count()
 
 
+# verify mode (include/cmix_amd.h, cmx_mixnet_set_verify): the report's classes
+VERIFY_CLASSES = {1: "layer-0 row", 2: "coded bit", 3: "selectors", 4: "decay (gather wave)", 5: "decay (tail-a wave)", 6: "decay (tail-b wave)",
+                  7: "ring written", 8: "ring read", 9: "layer-0 row segment"}
+VERIFY_CLASS = {"row": 1, "bit": 2, "sel": 3, "decay": 4, "decay_tail_a": 5, "decay_tail_b": 6, "ring_written": 7, "ring_read": 8, "segment": 9}
+
+
+def _verify_report(fn, h):
+    out = (C.c_uint64 * 8)()
+    if fn(h, out):
+        raise CmxError(last_error())
+    v = [int(x) for x in out]
+    none = (1 << 64) - 1
+    return {"chunks": v[0], "bits": v[1], "mismatches": v[2], "cls": v[3] if v[2] else None, "first_bit": v[4] if v[2] else None,
+            "mixer": None if v[5] == none or not v[2] else v[5], "row": None if v[6] == none or not v[2] else v[6],
+            "segment": None if v[7] == none or not v[2] else v[7]}
+
+
 def probe_libm(which, x, device=0):
     """which: 0 expf, 1 tanhf, 2 logistic; x: float32 ndarray -> float32 ndarray (device-evaluated)."""
     x = np.ascontiguousarray(x, np.float32)
@@ -202,6 +226,22 @@ class MixNet:
     def set_tolerance(self, on=True):
         """Tolerance mode (NOT bit-exact: layer-0 dot products as f64 tree sums): explicit, before the handle's first bit."""
         if lib().cmx_mixnet_set_tolerance(self.h, int(bool(on))):
+            raise CmxError(last_error())
+
+    def set_verify(self, on=True):
+        """Verify mode (include/cmix_amd.h): every word the network consumes checked against its source; explicit, before the handle's first bit."""
+        if lib().cmx_mixnet_set_verify(self.h, int(bool(on))):
+            raise CmxError(last_error())
+
+    def verify_report(self):
+        """dict: chunks, bits verified, mismatches, and of the first mismatch: cls (VERIFY_CLASSES), first_bit (its block's first stream bit), mixer, row,
+        segment (None where they do not apply). Synchronises the device."""
+        return _verify_report(lib().cmx_mixnet_verify_report, self.h)
+
+    def debug_verify_perturb(self, cls, bit, index, xor_mask):
+        """Test hook: one perturbation of class `cls` (number or VERIFY_CLASS key) for the next run (include/cmix_amd.h)."""
+        cls = VERIFY_CLASS.get(cls, cls)
+        if lib().cmx_mixnet_debug_verify_perturb(self.h, int(cls), int(bit), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def close(self):
@@ -571,6 +611,15 @@ class Pipeline:
         if lib().cmx_pipeline_set_tolerance(self.h, int(bool(on))):
             raise CmxError(last_error())
 
+    def set_verify(self, on=True):
+        """The mixing network's verify mode (include/cmix_amd.h): before the first chunk; wait / fetch / sync then fail on a mismatch."""
+        if lib().cmx_pipeline_set_verify(self.h, int(bool(on))):
+            raise CmxError(last_error())
+
+    def verify_report(self):
+        """as MixNet.verify_report"""
+        return _verify_report(lib().cmx_pipeline_verify_report, self.h)
+
     def mixnet_mode(self):
         """0 strict (bit-exact, the default), 1 tolerance -- as the library reports it"""
         return lib().cmx_pipeline_mixnet_mode(self.h)
@@ -814,6 +863,15 @@ class Predictor:
     def mode(self):
         n = C.c_int(0)
         return lib().cmx_mode(self.h, C.byref(n)), n.value
+
+    def set_verify(self, on=True):
+        """Verify mode of the look-ahead pipeline's mixing network: before the first stage_input; Predict then raises on a mismatch."""
+        if lib().cmx_set_verify(self.h, int(bool(on))):
+            raise CmxError(last_error())
+
+    def verify_report(self):
+        """as MixNet.verify_report (all zero unless the handle compresses)"""
+        return _verify_report(lib().cmx_verify_report, self.h)
 
     def decode_stream(self, code, nbytes):
         """Decoder::Decode over a whole stream inside the library (cmx_decode_stream): the arithmetic code behind the container header -> the nbytes

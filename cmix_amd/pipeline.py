@@ -59,7 +59,7 @@ class EngineStream:
     is for a compressor (reference src/predictor.cpp:361-469), a sub-chunk of known bytes at a time. feed() enqueues;
     finish() returns the container bytes (header + arithmetic code), identical to the reference binary's file."""
 
-    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None):
+    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", device_index)
@@ -78,6 +78,8 @@ class EngineStream:
         self.pipe = E.Pipeline(self.vocab, device_index, self.sub)
         self.pipe.enable_fxcm(None)
         self.pipe.enable_paq8()
+        if verify:   # the mixing network checks every word it consumes (include/cmix_amd.h, cmx_pipeline_set_verify): finish() raises on a mismatch
+            self.pipe.set_verify(True)
         self.pos = 0
         self.nsub = 0
         torch.cuda.synchronize(self.dev)

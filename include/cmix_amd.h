@@ -97,6 +97,13 @@ const float* cmx_debug_last_row(cmx_t*);
 int cmx_stage_input(cmx_t*, const uint8_t* bytes, size_t n);
 /* 0 = undecided (nothing built yet), 1 = per-bit stages, 2 = look-ahead pipeline; *chunks_in_flight (may be NULL). */
 int cmx_mode(cmx_t*, int* chunks_in_flight);
+/* Verify mode of the look-ahead pipeline's mixing network (cmx_pipeline_set_verify): before the first cmx_stage_input. cmx_predict then
+ * returns < 0 (cmx_last_error names the chunk, the stream bit and the kind of input) instead of a probability of a chunk in which a consumed word
+ * differs from its source; a compression either ends with every word the final network consumed checked or stops. A handle that decodes is
+ * not covered (the decoder's form of the network has no verify instantiation): its report stays at zero chunks. The programs in integration/
+ * switch it on with CMIX_VERIFY=1; the library reads no environment variable for it. cmx_verify_report: as cmx_mixnet_verify_report. */
+int cmx_set_verify(cmx_t*, int on);
+int cmx_verify_report(cmx_t*, uint64_t out[8]);
 void cmx_destroy(cmx_t*);
 
 /* ------------------------------------------------------------------------
@@ -168,6 +175,29 @@ int cmx_mixnet_spec_stats(cmx_mixnet_t*, uint64_t out[5]);
 /* Test hook (state injection): the network as after `steps` bits of a stream -- Mixer::steps_ (mixer.cpp:58,61) of all 47 mixers. The wrap / threshold
  * fixtures of tests/golden/make_wrap_traces.py place the reference's counters the same way (oracle/ref_harness.cpp). Between chunks only. */
 int cmx_mixnet_debug_set_steps(cmx_mixnet_t*, uint64_t steps);
+/* VERIFY MODE (opt-in; off by default, and then nothing of it is allocated or launched). Before the first bit, like cmx_mixnet_set_tolerance;
+ * refused together with tolerance mode and on a handle that runs the decoder's (late) kernel, and chunks only (the bit-synchronous calls are
+ * refused). Every chunk then runs cmx_mixnet_spec_verify_kernel -- the same roles and results as cmx_mixnet_spec_kernel, each also folding the
+ * words it loaded into 64-bit block sums (src/cmx_verify.h: a splitmix64-style mix of (class, bit, index, word), summed mod 2^64 over blocks of
+ * 64 bits) -- and, behind it on the same stream, cmx_mixnet_verify_kernel, which recomputes every block sum from the buffers in HBM: the raw
+ * inputs, the coded bits, the selectors, the decay schedule (as the gather and both tail waves loaded it) and the stretched inputs the in-launch
+ * ring carried (as the stretch waves stored them and as each helper loaded its slice). The helpers also store a digest with every layer-0 row
+ * segment they write back (words 0..2077; a ~8 MB table of the handle) and check it when they load the segment again. A mismatch changes no
+ * result and no control flow: it is counted in a sticky record, cmx_mixnet_sync fails naming it, cmx_pipeline_wait fails the chunk.
+ * cmx_mixnet_verify_report: out[0] chunks verified, [1] bits verified, [2] mismatches (blocks x class, x helper for the ring read, or row
+ * segments), then of the first one: [3] class (1 layer-0 row, 2 coded bit, 3 selectors, 4/5/6 decay as the gather / tail-a / tail-b wave
+ * loaded it, 7 ring written, 8 ring read, 9 row segment), [4] its block's first stream bit, [5] mixer (ring read, row segment), [6] row,
+ * [7] segment (row segment); UINT64_MAX where a field does not apply. Synchronises the device. */
+int cmx_mixnet_set_verify(cmx_mixnet_t*, int on);
+int cmx_mixnet_verify_on(cmx_mixnet_t*);
+int cmx_mixnet_verify_report(cmx_mixnet_t*, uint64_t out[8]);
+const unsigned long long* cmx_mixnet_verify_record(cmx_mixnet_t*);   /* DEVICE address of the 8 report words (NULL before verify mode was first on) */
+/* TEST HOOK of verify mode: one perturbation for the next chunk, a data mismatch reported as an error return (no kernel stops early, no wait
+ * times out). cls 1 / 2 / 3 / 4..6 (layer-0 row, coded bit, selectors, decay): word `index` of chunk bit `bit` of the caller's buffer (of the
+ * handle's decay schedule) is XORed with xor_mask between the network kernel and the verify kernel, and back after it; cls 7 / 8 (ring): the
+ * stretch wave stores stretched input `index` of chunk bit `bit` XOR xor_mask and folds the value it computed; cls 9 (row segment): `bit` =
+ * mixer * 10001 + row, weight `index` (< 2078) of that layer-0 row is XORed before the next kernel. */
+int cmx_mixnet_debug_verify_perturb(cmx_mixnet_t*, int cls, uint64_t bit, uint64_t index, uint32_t xor_mask);
 
 /* ------------------------------------------------------------------------
  * 2b. Stage: byte-level LSTM byte mixer = ByteMixer + Lstm + LstmLayer + its ByteModel bit
@@ -440,6 +470,11 @@ int cmx_pipeline_spec_stats(cmx_pipeline_t*, uint64_t out[5]);
 int cmx_pipeline_paq8_profile(cmx_pipeline_t*, unsigned long long out128[128]);
 int cmx_pipeline_ppmd_arena(cmx_pipeline_t*, uint64_t out3[3]);
 int cmx_pipeline_set_tolerance(cmx_pipeline_t*, int on);
+/* the mixing network's verify mode for this stream (cmx_mixnet_set_verify), before the first chunk: the record is copied back behind every chunk's
+ * network, and cmx_pipeline_wait (and _fetch) fail the chunk in which a mismatch showed, with the record in the message, and void the handle;
+ * _verify_report as cmx_mixnet_verify_report */
+int cmx_pipeline_set_verify(cmx_pipeline_t*, int on);
+int cmx_pipeline_verify_report(cmx_pipeline_t*, uint64_t out[8]);
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t*);
 /* Predictor::Pretrain over n dictionary bytes (HOST pointer), before the first submit: only the stages holding
  * `models_` learn (today: contexts + small models); mixers, SSE, LSTM and PPMd are not trained (predictor.cpp:471-487). */

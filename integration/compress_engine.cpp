@@ -123,6 +123,10 @@ int main(int argc, char* argv[]) {
   if (!hn) Predictor::Die();
   const double t_pre = since();
   Predictor p(vocab, kChunk);
+  {   // CMIX_VERIFY=1: the mixing network checks every word it consumes; a mismatch stops the program before a wrong file is written
+    const char* ver = getenv("CMIX_VERIFY");
+    if (ver && ver[0] == '1' && cmx_pipeline_set_verify(p.pipe(), 1)) Predictor::Die();
+  }
   const double t_ready = since();
   if (enable_preprocess) preprocessor::Pretrain(&p, dictionary);
   p.FlushPretrain();

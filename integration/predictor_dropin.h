@@ -47,6 +47,9 @@ class Predictor {
     const char* dev = getenv("CMIX_DEVICE");
     h_ = cmx_create(v, dictionary_path, dev ? atoi(dev) : 0);
     if (!h_) Die();
+    // CMIX_VERIFY=1: the mixing network checks every word it consumes; a mismatch stops the program before a wrong file is finished (a decoder is not covered)
+    const char* ver = getenv("CMIX_VERIFY");
+    if (ver && ver[0] == '1' && cmx_set_verify(h_, 1)) Die();
   }
   ~Predictor() { cmx_destroy(h_); }
   Predictor(const Predictor&) = delete;
