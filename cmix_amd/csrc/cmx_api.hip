@@ -564,6 +564,14 @@ int cmx_mixnet_debug_verify_perturb(cmx_mixnet_t* h, int cls, uint64_t bit, uint
   h->pert.cls = cls; h->pert.bit = bit; h->pert.index = index; h->pert.mask = xor_mask;
   return 0;
 }
+// mixnet_vote.hip (cmx_mixnet_state_diff, cmx_mixnet_debug_state_xor): the handle's state block -- the host copy of its pointers, the block's DEVICE address -- and its device
+int cmx_mixnet_state_view(cmx_mixnet_t* h, const MixState** host, MixState** dev, int* device) {
+  if (!h || !h->d_state) { set_err("cmx_mixnet_state_view: null handle"); return 1; }
+  if (host) *host = &h->h_state;
+  if (dev) *dev = h->d_state;
+  if (device) *device = h->device;
+  return 0;
+}
 // DEVICE address of MixState::error (set by a chunk kernel whose bounded in-launch wait ran out), for callers that copy it back in
 // stream order behind the chunk's kernel (cmx_pipeline_finish) instead of synchronising the device
 const int* cmx_mixnet_error_flag(cmx_mixnet_t* h) { return h ? &h->d_state->error : nullptr; }

@@ -82,6 +82,7 @@ struct cmx_engine {
   std::string dict;               // the hidden global `dictionary_path` (runner.cpp:17), read by the fxcm stage
   bool has_dict = false;
   bool verify = false;            // cmx_set_verify: the look-ahead pipeline's mixing network runs in verify mode
+  int shadow = 0;                 // cmx_set_shadow: shadow mixing networks of the look-ahead pipeline, voting on every chunk
   int mode = 0;                   // 0 undecided, 1 per-bit stages built (columns from the caller), 2 look-ahead pipeline built, 3 the decoder's pipeline (late-bit protocol)
   LookAhead* la = nullptr;
   cmx_pipeline_t* late = nullptr; // mode 3: every model family on the device, bits arriving one at a time (cmx_pipeline_late_*)
@@ -318,7 +319,8 @@ int ensure_lookahead(cmx_engine* h) {
   h->la = la;
   la->pipe = cmx_pipeline_create(h->vocab, h->device, kLaChunk);
   bool ok = la->pipe && cmx_pipeline_enable_fxcm(la->pipe, h->has_dict ? h->dict.c_str() : nullptr) == 0 &&
-            cmx_pipeline_enable_paq8(la->pipe) == 0 && (!h->verify || cmx_pipeline_set_verify(la->pipe, 1) == 0);
+            cmx_pipeline_enable_paq8(la->pipe) == 0 && (!h->verify || cmx_pipeline_set_verify(la->pipe, 1) == 0) &&
+            (!h->shadow || cmx_pipeline_set_shadow(la->pipe, h->shadow) == 0);
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
   const size_t T = 8 * kLaChunk;
   for (size_t i = 0; ok && i < kLaSlots; ++i) {
@@ -643,6 +645,20 @@ int cmx_verify_report(cmx_t* h, uint64_t out[8]) {
   if (!h || !out) { cmx_set_err("cmx_verify_report: bad argument"); return 1; }
   if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing verified: not a compressor's handle, or nothing staged yet)
   return cmx_pipeline_verify_report(h->la->pipe, out);
+}
+
+// shadow mixing networks of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
+int cmx_set_shadow(cmx_t* h, int k) {
+  if (!h) { cmx_set_err("cmx_set_shadow: null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err("cmx_set_shadow: k must be 0, 1 or 2 shadow mixing networks"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  h->shadow = k;
+  return 0;
+}
+int cmx_shadow_report(cmx_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_shadow_report: bad argument"); return 1; }
+  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
+  return cmx_pipeline_shadow_report(h->la->pipe, out);
 }
 
 // 0 undecided, 1 per-bit stages, 2 look-ahead pipeline; in mode 2 *chunks_in_flight (may be NULL) = submitted - used up

@@ -1,0 +1,373 @@
+// mixnet_vote.hip -- the redundant mixing-network vote (C ABI: cmx_vote_*, cmx_mixnet_state_diff, cmx_mixnet_debug_state_xor in include/cmix_amd.h).
+//
+// Verify mode (cmx_verify.h) checks every word the network LOADS from HBM against its source. What it cannot see is what the network computes with
+// those words: the main workgroup's LDS, the layer-1 / layer-2 rows, the extras, row_steps, the SSE cells. The complementary guard is redundancy:
+// the unchanged cmx_mixnet_spec_kernel runs on two or three handles over the same inputs, and two new kernels compare what they produced.
+//
+//   cmx_vote_kernel        every chunk: the final p and the 47 mixer outputs of every bit of n = 2 or 3 instances, word for word
+//   cmx_vote_fold_kernel   behind it: folds the chunk's result into a sticky record and captures the first differing bit
+//   cmx_state_diff_kernel  after an event (and in tests): every word of two handles' MixState arrays in HBM
+//
+// Out of scope here: continuing a stream on the majority after an event (the handle is voided, as in verify mode), and the decoder's form of the
+// network (a decoder's bits arrive one at a time from the host; its pipeline allocates nothing of this).
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+#include <string>
+
+#include "../../include/cmix_amd.h"
+#include "mixnet_state.h"
+
+void cmx_set_err(const std::string& s);  // cmx_api.hip
+extern "C" int cmx_mixnet_state_view(cmx_mixnet_t* h, const MixState** host, MixState** dev, int* device);   // cmx_api.hip
+
+namespace {
+constexpr unsigned long long kNone = ~0ull;
+constexpr int kCols = CMX_MIXERS + 1;   // 47 mixer outputs, then the final p: the causal order within a bit
+
+// device block of a vote handle
+struct VoteDev {
+  unsigned long long rec[8];     // the sticky record (cmx_vote_report)
+  unsigned long long key;        // this chunk: min over non-agreeing elements of (e << 2 | odd instance, 3 = no majority); ~0 = none
+  unsigned long long cnt;        // this chunk: non-agreeing elements
+  unsigned long long pad[6];
+  uint32_t words[3 * kCols];     // capture of the first event's bit: instance i, column c at [i * 48 + c]
+  uint32_t sel[CMX_MIXERS];
+  uint32_t bit;
+};
+struct VoteArgs {
+  const uint32_t* p[3];
+  const uint32_t* mix[3];
+};
+
+// one element of n instances: 0 agree, else 1 + (odd instance, 3 = no majority)
+template <int N>
+__device__ __forceinline__ unsigned vote_one(uint32_t a, uint32_t b, uint32_t c) {
+  if (N == 2) return a == b ? 0u : 4u;
+  if (a == b && b == c) return 0u;
+  if (b == c) return 1u;
+  if (a == c) return 2u;
+  if (a == b) return 3u;
+  return 4u;
+}
+
+// Items: [0, nq) quads of the flat mix arrays, [nq, nq + pq) quads of p, then the single words either array has left over (all of them when an
+// array is not 16-byte aligned: vec == 0). Every lane keeps its own minimum key and count; one reduction per wave at the end.
+template <int N>
+__global__ void __launch_bounds__(256) cmx_vote_kernel(VoteArgs a, unsigned long long nbits, int vec, VoteDev* d) {
+  const unsigned long long nmix = nbits * CMX_MIXERS;
+  const unsigned long long nq = vec ? nmix / 4 : 0, pq = vec ? nbits / 4 : 0;
+  const unsigned long long mt = nmix - 4 * nq, pt = nbits - 4 * pq;
+  const unsigned long long items = nq + pq + mt + pt;
+  unsigned long long key = kNone, cnt = 0;
+  auto mixword = [&](unsigned long long f, uint32_t w0, uint32_t w1, uint32_t w2) {
+    const unsigned r = vote_one<N>(w0, w1, w2);
+    if (r) {
+      const unsigned long long t = f / CMX_MIXERS, c = f - t * CMX_MIXERS;
+      const unsigned long long k = ((t * kCols + c) << 2) | (r - 1);
+      key = k < key ? k : key; ++cnt;
+    }
+  };
+  auto pword = [&](unsigned long long t, uint32_t w0, uint32_t w1, uint32_t w2) {
+    const unsigned r = vote_one<N>(w0, w1, w2);
+    if (r) {
+      const unsigned long long k = ((t * kCols + CMX_MIXERS) << 2) | (r - 1);
+      key = k < key ? k : key; ++cnt;
+    }
+  };
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * blockDim.x) {
+    if (i < nq + pq) {
+      const bool ism = i < nq;
+      const unsigned long long q = ism ? i : i - nq;
+      const uint4 v0 = reinterpret_cast<const uint4*>(ism ? a.mix[0] : a.p[0])[q];
+      const uint4 v1 = reinterpret_cast<const uint4*>(ism ? a.mix[1] : a.p[1])[q];
+      const uint4 v2 = N == 3 ? reinterpret_cast<const uint4*>(ism ? a.mix[2] : a.p[2])[q] : v1;
+      if (v0.x != v1.x || v0.y != v1.y || v0.z != v1.z || v0.w != v1.w || v0.x != v2.x || v0.y != v2.y || v0.z != v2.z || v0.w != v2.w) {
+        if (ism) { mixword(4 * q, v0.x, v1.x, v2.x); mixword(4 * q + 1, v0.y, v1.y, v2.y); mixword(4 * q + 2, v0.z, v1.z, v2.z); mixword(4 * q + 3, v0.w, v1.w, v2.w); }
+        else { pword(4 * q, v0.x, v1.x, v2.x); pword(4 * q + 1, v0.y, v1.y, v2.y); pword(4 * q + 2, v0.z, v1.z, v2.z); pword(4 * q + 3, v0.w, v1.w, v2.w); }
+      }
+    } else if (i < nq + pq + mt) {
+      const unsigned long long f = 4 * nq + (i - nq - pq);
+      mixword(f, a.mix[0][f], a.mix[1][f], N == 3 ? a.mix[2][f] : a.mix[1][f]);
+    } else {
+      const unsigned long long t = 4 * pq + (i - nq - pq - mt);
+      pword(t, a.p[0][t], a.p[1][t], N == 3 ? a.p[2][t] : a.p[1][t]);
+    }
+  }
+  if (__ballot(cnt != 0) == 0) return;   // (wave-uniform) nothing differed in this wave
+  for (int o = 32; o; o >>= 1) {
+    const unsigned long long k2 = __shfl_xor(key, o), c2 = __shfl_xor(cnt, o);
+    key = k2 < key ? k2 : key; cnt += c2;
+  }
+  if ((threadIdx.x & 63) == 0) { atomicMin(&d->key, key); atomicAdd(&d->cnt, cnt); }
+}
+
+// one wave, behind the vote kernel on the same stream: the chunk's key and count into the sticky record; the first event's bit is captured
+__global__ void cmx_vote_fold_kernel(VoteArgs a, unsigned long long nbits, unsigned long long bit0, int n, const uint32_t* sel, const uint8_t* bits, VoteDev* d) {
+  const unsigned long long key = d->key, cnt = d->cnt;
+  const bool first = cnt != 0 && d->rec[3] == 0;   // (read by every lane before lane 0 writes: one wave, the barrier below orders it)
+  __syncthreads();
+  const unsigned long long e = key >> 2, t = e / kCols, c = e - t * kCols;
+  if (first && t < nbits) {
+    for (int i = threadIdx.x; i < n * kCols; i += blockDim.x) {
+      const int inst = i / kCols, col = i - inst * kCols;
+      d->words[i] = col < CMX_MIXERS ? a.mix[inst][t * CMX_MIXERS + col] : a.p[inst][t];
+    }
+    for (int i = threadIdx.x; i < CMX_MIXERS; i += blockDim.x) d->sel[i] = sel ? sel[t * CMX_MIXERS + i] : 0u;
+  }
+  if (threadIdx.x == 0) {
+    d->rec[0] += 1; d->rec[1] += nbits; d->rec[2] = (unsigned long long)n;
+    if (cnt) d->rec[3] += 1;
+    if (first) {
+      d->rec[4] = bit0 + t; d->rec[5] = c; d->rec[6] = (key & 3) == 3 ? kNone : (key & 3); d->rec[7] = cnt;
+      d->bit = bits && t < nbits ? bits[t] : 0u;
+    }
+    d->key = kNone; d->cnt = 0;   // the next chunk starts clean
+  }
+}
+
+// ---- state diff: words of two arrays; per call one region ----
+struct DiffDev {
+  unsigned long long cnt, first, mask, pad;
+};
+// per_mixer: words per mixer of the region (0: the region has no mixer mask)
+__global__ void __launch_bounds__(256) cmx_state_diff_kernel(const uint32_t* x, const uint32_t* y, unsigned long long n, unsigned long long per_mixer, DiffDev* d) {
+  const unsigned long long nq = n / 4, items = nq + (n - 4 * nq);
+  unsigned long long first = kNone, cnt = 0, mask = 0;
+  auto word = [&](unsigned long long i) {
+    ++cnt; first = i < first ? i : first;
+    if (per_mixer) mask |= 1ull << (i / per_mixer);
+  };
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * blockDim.x) {
+    if (i < nq) {
+      const uint4 u = reinterpret_cast<const uint4*>(x)[i], v = reinterpret_cast<const uint4*>(y)[i];
+      if (u.x != v.x) word(4 * i);
+      if (u.y != v.y) word(4 * i + 1);
+      if (u.z != v.z) word(4 * i + 2);
+      if (u.w != v.w) word(4 * i + 3);
+    } else {
+      const unsigned long long j = 4 * nq + (i - nq);
+      if (x[j] != y[j]) word(j);
+    }
+  }
+  if (__ballot(cnt != 0) == 0) return;
+  for (int o = 32; o; o >>= 1) {
+    const unsigned long long f2 = __shfl_xor(first, o), c2 = __shfl_xor(cnt, o), m2 = __shfl_xor(mask, o);
+    first = f2 < first ? f2 : first; cnt += c2; mask |= m2;
+  }
+  if ((threadIdx.x & 63) == 0) { atomicMin(&d->first, first); atomicAdd(&d->cnt, cnt); if (mask) atomicOr(&d->mask, mask); }
+}
+
+constexpr unsigned long long kR = CMX_ROWS_PER_MIXER;
+constexpr int kRegions = 11;
+constexpr unsigned long long kScalarWords = (CMX_MIXERS + 1) + 2 * (CMX_MIXERS + 1) + 2 + 3;   // n_rows, max_steps, steps, sse_j / pc / ffl
+struct Region { const uint32_t* p; unsigned long long words, per_mixer; };
+void regions_of(const MixState& S, Region r[10]) {
+  r[0] = {(const uint32_t*)S.rows0, (unsigned long long)CMX_MIX0 * kR * CMX_ROW0_STRIDE, kR * CMX_ROW0_STRIDE};
+  r[1] = {(const uint32_t*)S.rows1, (unsigned long long)CMX_MIX1 * kR * CMX_ROW1_STRIDE, kR * CMX_ROW1_STRIDE};
+  r[2] = {(const uint32_t*)S.rows2, kR * CMX_ROW2_STRIDE, kR * CMX_ROW2_STRIDE};
+  r[3] = {(const uint32_t*)S.row_steps, (unsigned long long)CMX_MIXERS * kR * 2, 0};
+  r[4] = {(const uint32_t*)S.map_keys, (unsigned long long)CMX_MIXERS * CMX_MAP_SLOTS, 0};
+  r[5] = {(const uint32_t*)S.map_vals, (unsigned long long)CMX_MIXERS * CMX_MAP_SLOTS, 0};
+  r[6] = {(const uint32_t*)S.s6, (unsigned long long)CMX_SM6_VOL * 4, 0};
+  r[7] = {(const uint32_t*)S.s7, (unsigned long long)CMX_SM7_VOL * 4, 0};
+  r[8] = {(const uint32_t*)S.x1, (unsigned long long)CMX_MIX1_VOL, 0};
+  r[9] = {(const uint32_t*)S.x2, (unsigned long long)CMX_MIX2_VOL, 0};
+}
+// region 10: the scalars of a MixState block (host copy of the DEVICE block) as words, in the order n_rows, max_steps, steps, sse_j, sse_pc, sse_ffl
+void scalar_words(const MixState& S, uint32_t w[kScalarWords]) {
+  size_t k = 0;
+  memcpy(w + k, S.n_rows, sizeof S.n_rows); k += CMX_MIXERS + 1;
+  memcpy(w + k, S.max_steps, sizeof S.max_steps); k += 2 * (CMX_MIXERS + 1);
+  memcpy(w + k, &S.steps, 8); k += 2;
+  w[k++] = S.sse_j; w[k++] = S.sse_pc; w[k++] = S.sse_ffl;
+}
+// byte offset of scalar word `index` inside MixState
+size_t scalar_offset(unsigned long long index) {
+  if (index < CMX_MIXERS + 1) return offsetof(MixState, n_rows) + 4 * index;
+  index -= CMX_MIXERS + 1;
+  if (index < 2 * (CMX_MIXERS + 1)) return offsetof(MixState, max_steps) + 4 * index;
+  index -= 2 * (CMX_MIXERS + 1);
+  if (index < 2) return offsetof(MixState, steps) + 4 * index;
+  index -= 2;
+  return index == 0 ? offsetof(MixState, sse_j) : index == 1 ? offsetof(MixState, sse_pc) : offsetof(MixState, sse_ffl);
+}
+// (mixer, row, index) of word i of a region; kNone where a field does not apply
+void locate(int region, unsigned long long i, unsigned long long out[3]) {
+  out[0] = out[1] = kNone; out[2] = i;
+  switch (region) {
+    case 0: out[0] = i / (kR * CMX_ROW0_STRIDE); out[1] = i / CMX_ROW0_STRIDE % kR; out[2] = i % CMX_ROW0_STRIDE; break;
+    case 1: out[0] = CMX_MIX0 + i / (kR * CMX_ROW1_STRIDE); out[1] = i / CMX_ROW1_STRIDE % kR; out[2] = i % CMX_ROW1_STRIDE; break;
+    case 2: out[0] = CMX_MIXERS - 1; out[1] = i / CMX_ROW2_STRIDE; out[2] = i % CMX_ROW2_STRIDE; break;
+    case 3: out[0] = i / 2 / kR; out[1] = i / 2 % kR; out[2] = i % 2; break;
+    case 4: case 5: out[0] = i / CMX_MAP_SLOTS; out[2] = i % CMX_MAP_SLOTS; break;
+    default: break;
+  }
+}
+// the inverse, with bounds: word number inside the region, or kNone
+unsigned long long word_of(int region, unsigned long long mixer, unsigned long long row, unsigned long long index, const Region r[10]) {
+  switch (region) {
+    case 0: return mixer < CMX_MIX0 && row < kR && index < CMX_ROW0_STRIDE ? (mixer * kR + row) * CMX_ROW0_STRIDE + index : kNone;
+    case 1: return mixer >= CMX_MIX0 && mixer < CMX_MIX0 + CMX_MIX1 && row < kR && index < CMX_ROW1_STRIDE ? ((mixer - CMX_MIX0) * kR + row) * CMX_ROW1_STRIDE + index : kNone;
+    case 2: return (mixer == CMX_MIXERS - 1 || mixer == kNone) && row < kR && index < CMX_ROW2_STRIDE ? row * CMX_ROW2_STRIDE + index : kNone;
+    case 3: return mixer < CMX_MIXERS && row < kR && index < 2 ? (mixer * kR + row) * 2 + index : kNone;
+    case 4: case 5: return mixer < CMX_MIXERS && index < CMX_MAP_SLOTS ? mixer * CMX_MAP_SLOTS + index : kNone;
+    case 6: case 7: case 8: case 9: return index < r[region].words ? index : kNone;
+    case 10: return index < kScalarWords ? index : kNone;
+    default: return kNone;
+  }
+}
+}  // namespace
+
+struct cmx_vote {
+  int device = 0, n = 0;
+  VoteDev* d = nullptr;
+};
+
+extern "C" {
+
+cmx_vote_t* cmx_vote_create(int device, int n) {
+  if (n != 2 && n != 3) { cmx_set_err("cmx_vote_create: n must be 2 or 3 instances"); return nullptr; }
+  if (cmx_device_count() <= 0) { cmx_set_err("cmx_vote_create: no HIP device visible (a gfx950 GPU is required)"); return nullptr; }
+  if (device < 0 || device >= cmx_device_count() || hipSetDevice(device) != hipSuccess) { cmx_set_err("cmx_vote_create: bad device index"); return nullptr; }
+  cmx_vote_t* v = new cmx_vote();
+  v->device = device; v->n = n;
+  VoteDev init;
+  memset(&init, 0, sizeof init);
+  init.key = kNone;
+  if (hipMalloc((void**)&v->d, sizeof(VoteDev)) != hipSuccess || hipMemcpy(v->d, &init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    if (v->d) (void)hipFree(v->d);
+    delete v;
+    cmx_set_err("cmx_vote_create: hipMalloc failed");
+    return nullptr;
+  }
+  return v;
+}
+
+void cmx_vote_destroy(cmx_vote_t* v) {
+  if (!v) return;
+  (void)hipSetDevice(v->device);
+  (void)hipDeviceSynchronize();
+  if (v->d) (void)hipFree(v->d);
+  delete v;
+}
+
+int cmx_vote_run(cmx_vote_t* v, const float* const* d_p, const float* const* d_mix, size_t nbits, uint64_t stream_bit0, const uint32_t* d_sel, const uint8_t* d_bits,
+                 void* stream) {
+  if (!v || !d_p || !d_mix) { cmx_set_err("cmx_vote_run: bad argument"); return 1; }
+  if (nbits == 0) return 0;
+  if (nbits > 0x7fffffff) { cmx_set_err("cmx_vote_run: chunk too large"); return 1; }
+  VoteArgs a;
+  memset(&a, 0, sizeof a);
+  int vec = 1;
+  for (int i = 0; i < v->n; ++i) {
+    if (!d_p[i] || !d_mix[i]) { cmx_set_err("cmx_vote_run: null array of instance " + std::to_string(i)); return 1; }
+    a.p[i] = (const uint32_t*)d_p[i]; a.mix[i] = (const uint32_t*)d_mix[i];
+    if (((uintptr_t)d_p[i] | (uintptr_t)d_mix[i]) & 15) vec = 0;   // 16-byte loads need every array aligned
+  }
+  if (hipSetDevice(v->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned long long words = (unsigned long long)nbits * kCols;
+  const unsigned long long items = vec ? words / 4 + 8 : words;
+  const unsigned grid = (unsigned)(items / 256 + 1 < 1024 ? items / 256 + 1 : 1024);
+  if (v->n == 3) hipLaunchKernelGGL(cmx_vote_kernel<3>, dim3(grid), dim3(256), 0, st, a, (unsigned long long)nbits, vec, v->d);
+  else hipLaunchKernelGGL(cmx_vote_kernel<2>, dim3(grid), dim3(256), 0, st, a, (unsigned long long)nbits, vec, v->d);
+  hipLaunchKernelGGL(cmx_vote_fold_kernel, dim3(1), dim3(64), 0, st, a, (unsigned long long)nbits, (unsigned long long)stream_bit0, v->n, d_sel, d_bits, v->d);
+  if (hipGetLastError() != hipSuccess) { cmx_set_err("cmx_vote_run: kernel launch failed"); return 1; }
+  return 0;
+}
+
+const unsigned long long* cmx_vote_record(cmx_vote_t* v) { return v && v->d ? v->d->rec : nullptr; }
+
+int cmx_vote_report(cmx_vote_t* v, uint64_t out[8]) {
+  if (!v || !out) { cmx_set_err("cmx_vote_report: bad argument"); return 1; }
+  unsigned long long r[8];
+  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(r, v->d->rec, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) {
+    cmx_set_err("cmx_vote_report: device error"); return 1;
+  }
+  for (int i = 0; i < 8; ++i) out[i] = r[i];
+  return 0;
+}
+
+int cmx_vote_values(cmx_vote_t* v, uint32_t words[144], uint32_t sel[47], uint32_t* bit) {
+  if (!v || !words) { cmx_set_err("cmx_vote_values: bad argument"); return 1; }
+  VoteDev h;
+  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&h, v->d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) {
+    cmx_set_err("cmx_vote_values: device error"); return 1;
+  }
+  memcpy(words, h.words, sizeof h.words);
+  if (sel) memcpy(sel, h.sel, sizeof h.sel);
+  if (bit) *bit = h.bit;
+  return 0;
+}
+
+int cmx_mixnet_state_diff(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20]) {
+  if (!a || !b || !out) { cmx_set_err("cmx_mixnet_state_diff: bad argument"); return 1; }
+  const MixState *ha = nullptr, *hb = nullptr; MixState *da = nullptr, *db = nullptr; int deva = 0, devb = 0;
+  if (cmx_mixnet_state_view(a, &ha, &da, &deva) || cmx_mixnet_state_view(b, &hb, &db, &devb)) return 1;
+  if (deva != devb) { cmx_set_err("cmx_mixnet_state_diff: the two handles live on different devices"); return 1; }
+  if (hipSetDevice(deva) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_mixnet_state_diff: device error"); return 1; }
+  Region ra[10], rb[10];
+  regions_of(*ha, ra); regions_of(*hb, rb);
+  DiffDev* d = nullptr;
+  DiffDev h[kRegions];
+  memset(h, 0, sizeof h);
+  for (DiffDev& x : h) x.first = kNone;
+  bool ok = hipMalloc((void**)&d, sizeof h) == hipSuccess && hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice) == hipSuccess;
+  for (int r = 0; ok && r < 10; ++r) {
+    const unsigned long long items = ra[r].words / 4 + 4;
+    const unsigned grid = (unsigned)(items / 256 + 1 < 4096 ? items / 256 + 1 : 4096);
+    hipLaunchKernelGGL(cmx_state_diff_kernel, dim3(grid), dim3(256), 0, 0, ra[r].p, rb[r].p, ra[r].words, ra[r].per_mixer, d + r);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  MixState sa, sb;
+  ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, d, sizeof(DiffDev) * 10, hipMemcpyDeviceToHost) == hipSuccess;
+  ok = ok && hipMemcpy(&sa, da, sizeof sa, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(&sb, db, sizeof sb, hipMemcpyDeviceToHost) == hipSuccess;
+  uint32_t wa[kScalarWords], wb[kScalarWords];
+  if (ok) {
+    scalar_words(sa, wa); scalar_words(sb, wb);
+    for (unsigned long long i = 0; i < kScalarWords; ++i)
+      if (wa[i] != wb[i]) { if (!h[10].cnt) h[10].first = i; h[10].cnt++; }
+  }
+  for (int i = 0; i < 20; ++i) out[i] = 0;
+  for (int i = 1; i <= 6; ++i) out[i] = kNone;
+  for (int r = 0; ok && r < kRegions; ++r) {
+    out[0] += h[r].cnt; out[7 + r] = h[r].cnt;
+    if (h[r].cnt && out[1] == kNone) {
+      unsigned long long loc[3];
+      locate(r, h[r].first, loc);
+      uint32_t x = 0, y = 0;
+      if (r < 10) ok = hipMemcpy(&x, ra[r].p + h[r].first, 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(&y, rb[r].p + h[r].first, 4, hipMemcpyDeviceToHost) == hipSuccess;
+      else { x = wa[h[r].first]; y = wb[h[r].first]; }
+      out[1] = (uint64_t)r; out[2] = loc[0]; out[3] = loc[1]; out[4] = loc[2]; out[5] = x; out[6] = y;
+    }
+  }
+  out[18] = h[0].mask;
+  out[19] = h[1].mask | (h[2].mask ? 1ull << CMX_MIX1 : 0);
+  if (d) (void)hipFree(d);
+  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_mixnet_state_diff: device error"); return 1; }
+  return 0;
+}
+
+int cmx_mixnet_debug_state_xor(cmx_mixnet_t* net, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
+  if (!net) { cmx_set_err("cmx_mixnet_debug_state_xor: null handle"); return 1; }
+  if (!xor_mask) { cmx_set_err("cmx_mixnet_debug_state_xor: a zero mask changes nothing"); return 1; }
+  const MixState* hs = nullptr; MixState* ds = nullptr; int dev = 0;
+  if (cmx_mixnet_state_view(net, &hs, &ds, &dev)) return 1;
+  Region r[10];
+  regions_of(*hs, r);
+  const unsigned long long w = word_of(region, mixer, row, index, r);
+  if (w == kNone) { cmx_set_err("cmx_mixnet_debug_state_xor: no such word (region, mixer, row, index out of range)"); return 1; }
+  uint32_t* p = region < 10 ? (uint32_t*)r[region].p + w : (uint32_t*)((char*)ds + scalar_offset(w));
+  uint32_t x = 0;
+  if (hipSetDevice(dev) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&x, p, 4, hipMemcpyDeviceToHost) != hipSuccess) {
+    cmx_set_err("cmx_mixnet_debug_state_xor: device error"); return 1;
+  }
+  x ^= xor_mask;
+  if (hipMemcpy(p, &x, 4, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_mixnet_debug_state_xor: device error"); return 1; }
+  return 0;
+}
+
+}  // extern "C"

@@ -126,6 +126,12 @@ struct Slot {
   hipEvent_t ev_p80 = nullptr, ev_p81 = nullptr;   // paq8 stage (opt-in)
   bool used = false;
   bool untimed = false;  // the chunk in this slot has not been added to the stage totals yet
+  // shadow mixing networks (cmx_pipeline_set_shadow): allocated at the first finish, nothing of it otherwise
+  float* d_shp[2] = {nullptr, nullptr};               // [8 max] p of shadow i + 1
+  float* d_shmix[3] = {nullptr, nullptr, nullptr};    // [8 max][47] mixer outputs of instance i (0: the stream's own network, unless cmx_pipeline_debug_mix_out supplies the area)
+  unsigned long long* h_vote = nullptr;               // pinned [8] the vote's record as it stood behind this chunk, then [2] the shadows' sticky hand-off flags
+  hipEvent_t ev_sh[2] = {nullptr, nullptr}, ev_vote = nullptr;
+  bool voted = false;                                  // this slot's chunk has a vote behind it: whoever waits for ev_mix1 also waits for ev_vote
 };
 }  // namespace
 
@@ -207,6 +213,11 @@ struct cmx_pipeline {
   int last_slot = -1;
   double tot_ms[3] = {0, 0, 0};  // HIP-event time of every finished chunk's stages since the last reset
   uint64_t tot_chunks = 0;
+  int shadow = 0;                // cmx_pipeline_set_shadow: shadow mixing networks beside h->mix (0 = off: nothing below exists)
+  hipStream_t s_sh[2] = {nullptr, nullptr};   // their streams (from the factory, at set_shadow: the queue budget refuses there)
+  cmx_mixnet_t* sh[2] = {nullptr, nullptr};   // created at the first finish
+  cmx_vote_t* vote = nullptr;
+  uint64_t vote_bits = 0;        // stream bits handed to the vote so far
   float* dbg_mix = nullptr;      // diagnosis (cmx_pipeline_debug_mix_out): the 47 mixer outputs of every bit, [bit][47], as far as dbg_mix_cap bits
   uint64_t dbg_mix_cap = 0, dbg_mix_bits = 0;
 };
@@ -232,10 +243,25 @@ static int probe_streams(cmx_pipeline* h) {
   hipStream_t q[24] = {h->s_lstm, h->s_ctx, h->s_mix, h->s_up, h->s_fx, h->s_p8, h->late ? h->late->s_bm : nullptr};
   int n = 7;
   if (h->p8) n += cmx_p8stage_streams(h->p8, q + n, 24 - n);
+  for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_sh[i];   // (null entries are skipped)
   const int all = cmx_overlap_probe(q, n, &h->probe_n);
   h->probe_all = all < 0 ? 0 : all;
   h->overlap = all < 0 ? -1 : all == h->probe_n ? 1 : 0;
   return h->overlap;
+}
+
+// a slot's chunk has left the mixing network -- and, with shadows, the vote behind it
+static hipError_t slot_done(Slot& s) {
+  const hipError_t e = hipEventSynchronize(s.ev_mix1);
+  return e == hipSuccess && s.voted ? hipEventSynchronize(s.ev_vote) : e;
+}
+// What a vote record (cmx_vote_report's eight words) says, for an error message
+static std::string vote_text(const unsigned long long r[8]) {
+  std::string s = "shadow vote: the " + std::to_string(r[2]) + " mixing-network instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream bit " +
+                  std::to_string(r[4]) + ", " + (r[5] < 47 ? "mixer " + std::to_string(r[5]) : std::string("final p")) + ": ";
+  if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
+  else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own network)" : "");
+  return s + " (the stream's output is void)";
 }
 
 __global__ void cmx_fxcm_hints_kernel(const float* layer0, long stride, const float* p_after, const int* ex, int T, int16_t* lstmpr, uint8_t* lstmex) {
@@ -274,6 +300,34 @@ static void wg_release(cmx_pipeline* h) {
   h->wgs = 0;
 }
 
+static void wg_unclaim(cmx_pipeline* h, int n) {
+  std::lock_guard<std::mutex> g(g_wg_mu);
+  g_wg_used[h->device & 63] -= n;
+  h->wgs -= n;
+}
+// everything cmx_pipeline_set_shadow and the first finish behind it made: the device is idle
+static void shadow_drop(cmx_pipeline* h) {
+  if (!h->shadow) return;
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();
+  cmx_vote_destroy(h->vote); h->vote = nullptr;
+  for (int i = 0; i < 2; ++i) {
+    cmx_mixnet_destroy(h->sh[i]); h->sh[i] = nullptr;
+    if (h->s_sh[i]) cmx_destroy_stream(h->s_sh[i]);
+    h->s_sh[i] = nullptr;
+  }
+  for (Slot& s : h->slot) {
+    for (float*& p : s.d_shp) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float*& p : s.d_shmix) { if (p) (void)hipFree(p); p = nullptr; }
+    if (s.h_vote) (void)hipHostFree(s.h_vote);
+    s.h_vote = nullptr;
+    for (hipEvent_t* e : {&s.ev_sh[0], &s.ev_sh[1], &s.ev_vote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    s.voted = false;
+  }
+  wg_unclaim(h, 27 * h->shadow);
+  h->shadow = 0;
+}
+
 void cmx_pipeline_destroy(cmx_pipeline_t* h) {
   if (!h) return;
   if (h->late) {
@@ -292,6 +346,7 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
     delete h->late;
     h->late = nullptr;
   }
+  shadow_drop(h);
   wg_release(h);
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
@@ -463,6 +518,7 @@ int cmx_pipeline_enable_paq8(cmx_pipeline_t* h) {
 int cmx_pipeline_set_tolerance(cmx_pipeline_t* h, int on) {
   if (!h) { cmx_set_err("cmx_pipeline_set_tolerance: null handle"); return 1; }
   if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_tolerance: only before the first chunk"); return 1; }
+  if (on && h->shadow) { cmx_set_err("cmx_pipeline_set_tolerance: shadow mixing networks are set (the vote compares strict kernels)"); return 1; }
   // the mixing network first (it can refuse: after the stream's first bit); the LSTM's switch (its weight-update contraction
   // on the matrix cores) follows and is rolled back with the network's if it fails, so that the two never disagree about the mode
   const int was = cmx_mixnet_mode(h->mix);
@@ -481,6 +537,72 @@ int cmx_pipeline_set_verify(cmx_pipeline_t* h, int on) {
 int cmx_pipeline_verify_report(cmx_pipeline_t* h, uint64_t out[8]) {
   if (!h) { cmx_set_err("cmx_pipeline_verify_report: null handle"); return 1; }
   return cmx_mixnet_verify_report(h->mix, out);
+}
+// ---- shadow mixing networks and their vote (include/cmix_amd.h; mixnet_vote.hip) ----
+// Reserves here what can be refused -- k streams of the factory (the queue budget) and 27 resident workgroups per shadow --; the k handles
+// (~2.8 GB each) and the per-slot buffers are made at the first finish.
+int cmx_pipeline_set_shadow(cmx_pipeline_t* h, int k) {
+  if (!h) { cmx_set_err("cmx_pipeline_set_shadow: null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err("cmx_pipeline_set_shadow: k must be 0, 1 or 2 shadow mixing networks (a vote has 2 or 3 instances)"); return 1; }
+  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_shadow: only before the first chunk"); return 1; }
+  if (k && (h->lstm_tolerance || cmx_mixnet_mode(h->mix) == 1)) { cmx_set_err("cmx_pipeline_set_shadow: the tolerance switch is set (the vote compares strict kernels)"); return 1; }
+  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  if (k == h->shadow) return 0;
+  shadow_drop(h);
+  if (k == 0) return probe_streams(h) < 0 ? 1 : 0;
+  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) {
+    cmx_set_err("cmx_pipeline_set_shadow: this process holds " + std::to_string(cmx_hw_queues(h->device)) + " dedicated hardware queues on device " + std::to_string(h->device) +
+                " and " + std::to_string(k) + " shadow mixing network(s) need one each, the limit is " + std::to_string(CMX_MAX_HW_QUEUES));
+    return 1;
+  }
+  if (!wg_claim(h, 27 * k, "cmx_pipeline_set_shadow")) return 1;
+  h->shadow = k;
+  for (int i = 0; i < k; ++i)
+    if (cmx_make_stream(&h->s_sh[i], 1)) { shadow_drop(h); return 1; }   // (the factory has said why)
+  return probe_streams(h) < 0 ? 1 : 0;
+}
+// the first finish with shadows: the handles, the vote, the per-slot buffers
+static int shadow_build(cmx_pipeline* h) {
+  const size_t T = 8 * h->max_chunk;
+  h->vote = cmx_vote_create(h->device, 1 + h->shadow);
+  if (!h->vote) return 1;
+  for (int i = 0; i < h->shadow; ++i) {
+    h->sh[i] = cmx_mixnet_create(h->device);
+    if (!h->sh[i] || cmx_mixnet_set_upload_stream(h->sh[i], h->s_up)) return 1;
+  }
+  bool ok = hipSetDevice(h->device) == hipSuccess;
+  for (Slot& s : h->slot) {
+    for (int i = 0; i < h->shadow; ++i) ok = ok && hipMalloc((void**)&s.d_shp[i], T * 4) == hipSuccess && hipEventCreateWithFlags(&s.ev_sh[i], hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i <= h->shadow; ++i) ok = ok && hipMalloc((void**)&s.d_shmix[i], T * CMX_N_MIXERS * 4) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&s.h_vote, 10 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_vote, hipEventDisableTiming) == hipSuccess;
+    if (ok) memset(s.h_vote, 0, 10 * 8);
+  }
+  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_finish: buffer allocation for the shadow mixing networks failed"); return 1; }
+  return 0;
+}
+int cmx_pipeline_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_pipeline_shadow_report: bad argument"); return 1; }
+  if (!h->vote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
+  return cmx_vote_report(h->vote, out);
+}
+int cmx_pipeline_shadow_values(cmx_pipeline_t* h, uint32_t words[144], uint32_t sel[47], uint32_t* bit) {
+  if (!h || !words) { cmx_set_err("cmx_pipeline_shadow_values: bad argument"); return 1; }
+  if (!h->vote) { memset(words, 0, 144 * 4); if (sel) memset(sel, 0, 47 * 4); if (bit) *bit = 0; return 0; }
+  return cmx_vote_values(h->vote, words, sel, bit);
+}
+static cmx_mixnet_t* shadow_instance(cmx_pipeline* h, int i) { return i == 0 ? h->mix : i > 0 && i <= h->shadow ? h->sh[i - 1] : nullptr; }
+int cmx_pipeline_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[20]) {
+  if (!h || !out) { cmx_set_err("cmx_pipeline_shadow_state_diff: bad argument"); return 1; }
+  cmx_mixnet_t *x = shadow_instance(h, a), *y = shadow_instance(h, b);
+  if (!x || !y) { cmx_set_err("cmx_pipeline_shadow_state_diff: no such instance (0 = the stream's network, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
+  return cmx_mixnet_state_diff(x, y, out);
+}
+int cmx_pipeline_debug_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
+  if (!h) { cmx_set_err("cmx_pipeline_debug_shadow_xor: null handle"); return 1; }
+  cmx_mixnet_t* x = shadow_instance(h, instance);
+  if (!x) { cmx_set_err("cmx_pipeline_debug_shadow_xor: no such instance (0 = the stream's network, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
+  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
+  return cmx_mixnet_debug_state_xor(x, region, mixer, row, index, xor_mask);
 }
 // 0 strict, 1 tolerance: not strict as soon as EITHER the mixing network or the LSTM computes in its tolerance form
 int cmx_pipeline_stage_overlap(cmx_pipeline_t* h) { return h ? h->overlap : -1; }
@@ -514,7 +636,7 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
   auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_mark = now();
   auto lap = [&](int k) { const double t = now(); h->host_ms[k] += t - t_mark; t_mark = t; };
-  if (s.used && hipEventSynchronize(s.ev_mix1) != hipSuccess) {  // the chunk that used these buffers kSlots submits ago
+  if (s.used && slot_done(s) != hipSuccess) {  // the chunk that used these buffers kSlots submits ago (and, with shadows, its vote)
     cmx_set_err("cmx_pipeline_begin: device error in an earlier chunk");
     return 1;
   }
@@ -651,12 +773,39 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
   float* dmix = nullptr;
   if (h->dbg_mix && h->dbg_mix_bits + 8 * n <= h->dbg_mix_cap) dmix = h->dbg_mix + h->dbg_mix_bits * 47;   // (CMX_MIXERS, mixnet_state.h)
   h->dbg_mix_bits += 8 * n;
+  if (h->shadow && !h->vote && shadow_build(h)) return 1;
+  if (h->shadow && !dmix) dmix = s.d_shmix[0];   // the vote compares every instance's 47 mixer outputs
   if (cmx_mixnet_run(h->mix, s.d_layer0, s.d_sel, s.d_bits, 8 * n, d_p_out, dmix, h->s_mix)) return 1;
   // the kernel's sticky time-out word, in stream order behind it: cmx_pipeline_wait looks at it per chunk (a look-ahead coder never
   // calls cmx_pipeline_sync, the only other place where it is read)
   (void)hipMemcpyAsync(&s.h_fail[2], cmx_mixnet_error_flag(h->mix), 4, hipMemcpyDeviceToHost, h->s_mix);
   if (cmx_mixnet_verify_on(h->mix)) (void)hipMemcpyAsync(s.h_vrec, cmx_mixnet_verify_record(h->mix), 64, hipMemcpyDeviceToHost, h->s_mix);   // (the same for verify mode's record)
   (void)hipEventRecord(s.ev_mix1, h->s_mix);
+  if (h->shadow) {   // ---- the same chunk on every shadow, from the slot's own rows / selectors / bits; then the vote on the last shadow's stream ----
+    const float* vp[3] = {d_p_out, nullptr, nullptr};
+    const float* vm[3] = {dmix, nullptr, nullptr};
+    const int k = h->shadow;
+    for (int i = 0; i < k; ++i) {
+      hipStream_t q = h->s_sh[i];
+      (void)hipStreamWaitEvent(q, s.ev_ctx1, 0);
+      (void)hipStreamWaitEvent(q, s.ev_lstm1, 0);
+      if (h->fxcm) (void)hipStreamWaitEvent(q, s.ev_fx1, 0);
+      if (h->p8) (void)hipStreamWaitEvent(q, s.ev_p81, 0);
+      if (cols) (void)hipStreamWaitEvent(q, s.ev_cols, 0);
+      if (cmx_mixnet_run(h->sh[i], s.d_layer0, s.d_sel, s.d_bits, 8 * n, s.d_shp[i], s.d_shmix[i + 1], q)) return 1;
+      (void)hipMemcpyAsync((unsigned*)(s.h_vote + 8) + i, cmx_mixnet_error_flag(h->sh[i]), 4, hipMemcpyDeviceToHost, q);
+      (void)hipEventRecord(s.ev_sh[i], q);
+      vp[i + 1] = s.d_shp[i]; vm[i + 1] = s.d_shmix[i + 1];
+    }
+    hipStream_t q = h->s_sh[k - 1];
+    (void)hipStreamWaitEvent(q, s.ev_mix1, 0);
+    for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_sh[i], 0);
+    if (cmx_vote_run(h->vote, vp, vm, 8 * n, h->vote_bits, s.d_sel, s.d_bits, q)) return 1;
+    (void)hipMemcpyAsync(s.h_vote, cmx_vote_record(h->vote), 64, hipMemcpyDeviceToHost, q);
+    (void)hipEventRecord(s.ev_vote, q);
+    s.voted = true;
+    h->vote_bits += 8 * n;
+  }
   s.d_p = d_p_out;
   h->host_ms[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fin).count();
   s.untimed = true;
@@ -745,7 +894,7 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
   if (index >= h->finished || index + kSlots < h->finished) { cmx_set_err("cmx_pipeline_wait: that chunk is not in flight"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   Slot& s = h->slot[index % kSlots];
-  if (hipEventSynchronize(s.ev_mix1) != hipSuccess) { cmx_set_err("cmx_pipeline_wait: device error"); return 1; }
+  if (slot_done(s) != hipSuccess) { cmx_set_err("cmx_pipeline_wait: device error"); return 1; }
   const bool p8fail = h->p8 && cmx_p8stage_mixfail(h->p8);   // (host-mapped: the paq8 mixer's workgroup 0 gave up waiting for another workgroup)
   if (s.h_fail[0] || s.h_fail[1] || s.h_fail[2] || p8fail) {
     cmx_set_err(std::string("cmx_pipeline_wait: an in-launch hand-off of the ") + (s.h_fail[0] ? "LSTM" : s.h_fail[1] ? "fxcm" : s.h_fail[2] ? "mixing network" : "paq8 mixer") +
@@ -757,6 +906,20 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
     cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + cmx_mixnet_verify_text(s.h_vrec));
     h->failed = true;
     return 1;
+  }
+  if (s.voted) {
+    const unsigned* shfail = (const unsigned*)(s.h_vote + 8);
+    if (shfail[0] || shfail[1]) {
+      cmx_set_err("cmx_pipeline_wait: an in-launch hand-off of shadow mixing network " + std::to_string(shfail[0] ? 1 : 2) + " timed out (workgroups not co-resident?): the vote is void from chunk " +
+                  std::to_string(index) + " on");
+      h->failed = true;
+      return 1;
+    }
+    if (s.h_vote[3]) {   // the instances disagreed in this chunk or an earlier one (the record is sticky)
+      cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + vote_text(s.h_vote));
+      h->failed = true;
+      return 1;
+    }
   }
   return 0;
 }
@@ -784,8 +947,15 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
   ok = hipStreamSynchronize(h->s_mix) == hipSuccess && ok;
   if (h->s_fx) ok = hipStreamSynchronize(h->s_fx) == hipSuccess && ok;
   if (h->p8) ok = cmx_p8stage_sync(h->p8) == 0 && ok;
+  for (hipStream_t q : h->s_sh) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (!ok) { cmx_set_err("cmx_pipeline_sync: device error"); h->failed = true; return 1; }
   if (cmx_ctxmodels_sync(h->ctx) || cmx_mixnet_sync(h->mix)) { h->failed = true; return 1; }
+  for (cmx_mixnet_t* m : h->sh) if (m && cmx_mixnet_sync(m)) { h->failed = true; return 1; }
+  if (h->vote) {
+    uint64_t r[8];
+    if (cmx_vote_report(h->vote, r)) { h->failed = true; return 1; }
+    if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + vote_text(t)); h->failed = true; return 1; }
+  }
   // the multi-workgroup kernels bound every in-launch wait: one that ran out left garbage behind, not a hang
   if (cmx_lstm_failed(h->lstm)) { cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the LSTM kernels timed out (workgroups not co-resident?): the stream's output is void"); h->failed = true; return 1; }
   if (h->fxcm && cmx_fxcm_failed(h->fxcm)) { cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the fxcm kernel timed out (workgroups not co-resident?): the stream's output is void"); h->failed = true; return 1; }
@@ -882,6 +1052,7 @@ int cmx_pipeline_late_start(cmx_pipeline_t* h, int last_bit) {
   if (h->compact) { cmx_set_err("cmx_pipeline_late_start: the stages share HIP streams (CMX_PIPELINE_STREAMS); a decoder needs every stage kernel running at once"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   if (hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_pipeline_late_start: device error"); return 1; }   // pretraining is complete
+  shadow_drop(h);   // a decoder is not covered by the vote (include/cmix_amd.h): it holds no stream, workgroup or buffer of it
   Late* L = new Late();
   h->late = L;
   const size_t n = kLateChunk, T = 8 * n;

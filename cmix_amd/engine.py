@@ -163,6 +163,23 @@ def lib():
         L.cmx_pipeline_verify_report.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_set_verify.argtypes = [C.c_void_p, C.c_int]
         L.cmx_verify_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_vote_create.restype = C.c_void_p
+        L.cmx_vote_create.argtypes = [C.c_int, C.c_int]
+        L.cmx_vote_destroy.argtypes = [C.c_void_p]
+        L.cmx_vote_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_vote_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_vote_record.restype = C.c_void_p
+        L.cmx_vote_record.argtypes = [C.c_void_p]
+        L.cmx_vote_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_mixnet_state_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_mixnet_debug_state_xor.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
+        L.cmx_pipeline_set_shadow.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_pipeline_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.cmx_pipeline_debug_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
+        L.cmx_set_shadow.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_pipeline_late_start.argtypes = [C.c_void_p, C.c_int]
         L.cmx_pipeline_late_predict.restype = C.c_float
         L.cmx_pipeline_late_predict.argtypes = [C.c_void_p]
@@ -205,6 +222,94 @@ def _verify_report(fn, h):
             "segment": None if v[7] == none or not v[2] else v[7]}
 
 
+# the redundant vote (include/cmix_amd.h, cmx_vote_*; the rule's specification is cmix_amd.vote.vote_reference)
+STATE_REGIONS = ("rows0", "rows1", "rows2", "row_steps", "map_keys", "map_vals", "s6", "s7", "x1", "x2", "scalars")
+_NONE64 = (1 << 64) - 1
+
+
+def _opt(v):
+    return None if v == _NONE64 else v
+
+
+def _vote_report(fn, h):
+    out = (C.c_uint64 * 8)()
+    if fn(h, out):
+        raise CmxError(last_error())
+    v = [int(x) for x in out]
+    ev = v[3] != 0
+    return {"chunks": v[0], "bits": v[1], "n": v[2], "events": v[3], "first_bit": v[4] if ev else None, "column": v[5] if ev else None,
+            "odd": _opt(v[6]) if ev else None, "elements": v[7] if ev else None, "raw": v}
+
+
+def _vote_values(fn, h, n):
+    words, sel, bit = np.zeros(144, np.uint32), np.zeros(47, np.uint32), C.c_uint32(0)
+    if fn(h, words.ctypes.data, sel.ctypes.data, C.byref(bit)):
+        raise CmxError(last_error())
+    return {"words": words[:48 * n].reshape(n, 48).copy(), "sel": sel, "bit": int(bit.value)}
+
+
+def _state_diff(out):
+    v = [int(x) for x in out]
+    first = None
+    if v[0]:
+        first = {"region": v[1], "mixer": _opt(v[2]), "row": _opt(v[3]), "index": _opt(v[4]), "a": v[5], "b": v[6]}
+    return {"words": v[0], "first": first, "per_region": dict(zip(STATE_REGIONS, v[7:18])), "layer0_mask": v[18], "layer12_mask": v[19], "raw": v}
+
+
+def _u64(v):
+    return _NONE64 if v is None else int(v)
+
+
+def _region(r):
+    return STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
+
+
+class Vote:
+    """The vote kernel over n = 2 or 3 instances' p [T] and mixer outputs [T, 47] (CUDA float32 / int32 / uint8 tensors of 4-byte words are all
+    taken as words); the record is sticky across run() calls."""
+
+    def __init__(self, n, device=0):
+        self.n = int(n)
+        self.h = lib().cmx_vote_create(device, self.n)
+        if not self.h:
+            raise CmxError(last_error())
+
+    def run(self, ps, mixes, stream_bit0=0, sel=None, bits=None, stream=None):
+        import torch
+        assert len(ps) == self.n and len(mixes) == self.n
+        T = int(ps[0].numel())
+        for p, m in zip(ps, mixes):
+            assert p.is_cuda and m.is_cuda and p.is_contiguous() and m.is_contiguous() and p.element_size() == 4 and m.element_size() == 4
+            assert p.numel() == T and m.numel() == T * N_MIXERS
+        if stream is None:
+            stream = torch.cuda.current_stream(ps[0].device).cuda_stream
+        ap = (C.c_void_p * 3)(*[p.data_ptr() for p in ps])
+        am = (C.c_void_p * 3)(*[m.data_ptr() for m in mixes])
+        if lib().cmx_vote_run(self.h, ap, am, T, int(stream_bit0), sel.data_ptr() if sel is not None else None,
+                              bits.data_ptr() if bits is not None else None, C.c_void_p(stream)):
+            raise CmxError(last_error())
+
+    def report(self):
+        """dict: chunks, bits, n, events (chunks with a non-agreeing element), and of the first event: first_bit, column (0..46 mixer, 47 final p),
+        odd (instance, None = no majority), elements; raw = the eight words. Synchronises the device."""
+        return _vote_report(lib().cmx_vote_report, self.h)
+
+    def values(self):
+        """the captured bit of the first event: words [n, 48] u32, sel [47] u32, bit"""
+        return _vote_values(lib().cmx_vote_values, self.h, self.n)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().cmx_vote_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def probe_libm(which, x, device=0):
     """which: 0 expf, 1 tanhf, 2 logistic; x: float32 ndarray -> float32 ndarray (device-evaluated)."""
     x = np.ascontiguousarray(x, np.float32)
@@ -242,6 +347,19 @@ class MixNet:
         """Test hook: one perturbation of class `cls` (number or VERIFY_CLASS key) for the next run (include/cmix_amd.h)."""
         cls = VERIFY_CLASS.get(cls, cls)
         if lib().cmx_mixnet_debug_verify_perturb(self.h, int(cls), int(bit), int(index), int(xor_mask)):
+            raise CmxError(last_error())
+
+    def state_diff(self, other):
+        """Every word of this handle's and `other`'s state in HBM compared (include/cmix_amd.h, cmx_mixnet_state_diff): dict words, first
+        (region, mixer, row, index, a, b -- None where a field does not apply), per_region, layer0_mask, layer12_mask, raw. Synchronises the device."""
+        out = (C.c_uint64 * 20)()
+        if lib().cmx_mixnet_state_diff(self.h, other.h, out):
+            raise CmxError(last_error())
+        return _state_diff(out)
+
+    def debug_state_xor(self, region, mixer, row, index, xor_mask):
+        """Test hook: XOR one state word (region: number or STATE_REGIONS name), between chunks."""
+        if lib().cmx_mixnet_debug_state_xor(self.h, _region(region), _u64(mixer), _u64(row), _u64(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def close(self):
@@ -620,6 +738,33 @@ class Pipeline:
         """as MixNet.verify_report"""
         return _verify_report(lib().cmx_pipeline_verify_report, self.h)
 
+    def set_shadow(self, k):
+        """k = 0 / 1 / 2 shadow mixing networks voting on every chunk (include/cmix_amd.h): before the first chunk; wait / fetch / sync then fail
+        the chunk in which the instances disagree."""
+        if lib().cmx_pipeline_set_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+        self._shadow = int(k)
+
+    def shadow_report(self):
+        """as Vote.report (all zero while nothing was voted)"""
+        return _vote_report(lib().cmx_pipeline_shadow_report, self.h)
+
+    def shadow_values(self):
+        """as Vote.values"""
+        return _vote_values(lib().cmx_pipeline_shadow_values, self.h, 1 + getattr(self, "_shadow", 0))
+
+    def shadow_state_diff(self, a, b):
+        """MixNet.state_diff of instances a and b (0 = the stream's own network, 1.. = the shadows)"""
+        out = (C.c_uint64 * 20)()
+        if lib().cmx_pipeline_shadow_state_diff(self.h, int(a), int(b), out):
+            raise CmxError(last_error())
+        return _state_diff(out)
+
+    def debug_shadow_xor(self, instance, region, mixer, row, index, xor_mask):
+        """Test hook: MixNet.debug_state_xor on one instance, between chunks."""
+        if lib().cmx_pipeline_debug_shadow_xor(self.h, int(instance), _region(region), _u64(mixer), _u64(row), _u64(index), int(xor_mask)):
+            raise CmxError(last_error())
+
     def mixnet_mode(self):
         """0 strict (bit-exact, the default), 1 tolerance -- as the library reports it"""
         return lib().cmx_pipeline_mixnet_mode(self.h)
@@ -872,6 +1017,15 @@ class Predictor:
     def verify_report(self):
         """as MixNet.verify_report (all zero unless the handle compresses)"""
         return _verify_report(lib().cmx_verify_report, self.h)
+
+    def set_shadow(self, k):
+        """Shadow mixing networks of the look-ahead pipeline (include/cmix_amd.h, cmx_set_shadow): before the first stage_input / Predict."""
+        if lib().cmx_set_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+
+    def shadow_report(self):
+        """as Vote.report (all zero unless the handle compresses)"""
+        return _vote_report(lib().cmx_shadow_report, self.h)
 
     def decode_stream(self, code, nbytes):
         """Decoder::Decode over a whole stream inside the library (cmx_decode_stream): the arithmetic code behind the container header -> the nbytes

@@ -59,7 +59,7 @@ class EngineStream:
     is for a compressor (reference src/predictor.cpp:361-469), a sub-chunk of known bytes at a time. feed() enqueues;
     finish() returns the container bytes (header + arithmetic code), identical to the reference binary's file."""
 
-    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False):
+    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", device_index)
@@ -80,6 +80,8 @@ class EngineStream:
         self.pipe.enable_paq8()
         if verify:   # the mixing network checks every word it consumes (include/cmix_amd.h, cmx_pipeline_set_verify): finish() raises on a mismatch
             self.pipe.set_verify(True)
+        if shadow:   # that many shadow mixing networks vote on every sub-chunk's probabilities (cmx_pipeline_set_shadow): finish() raises on a disagreement
+            self.pipe.set_shadow(shadow)
         self.pos = 0
         self.nsub = 0
         torch.cuda.synchronize(self.dev)

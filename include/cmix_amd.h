@@ -104,6 +104,12 @@ int cmx_mode(cmx_t*, int* chunks_in_flight);
  * switch it on with CMIX_VERIFY=1; the library reads no environment variable for it. cmx_verify_report: as cmx_mixnet_verify_report. */
 int cmx_set_verify(cmx_t*, int on);
 int cmx_verify_report(cmx_t*, uint64_t out[8]);
+/* Shadow mixing networks of the look-ahead pipeline (cmx_pipeline_set_shadow, k = 0 / 1 / 2): before the first cmx_stage_input or cmx_predict.
+ * cmx_predict then returns < 0 instead of a probability of a chunk in which the instances disagreed. A handle that decodes is not covered: its
+ * report stays at zero chunks. The programs in integration/ read CMIX_SHADOW=1|2; the library reads no environment variable for it.
+ * cmx_shadow_report: as cmx_vote_report. */
+int cmx_set_shadow(cmx_t*, int k);
+int cmx_shadow_report(cmx_t*, uint64_t out[8]);
 void cmx_destroy(cmx_t*);
 
 /* ------------------------------------------------------------------------
@@ -198,6 +204,42 @@ const unsigned long long* cmx_mixnet_verify_record(cmx_mixnet_t*);   /* DEVICE a
  * stretch wave stores stretched input `index` of chunk bit `bit` XOR xor_mask and folds the value it computed; cls 9 (row segment): `bit` =
  * mixer * 10001 + row, weight `index` (< 2078) of that layer-0 row is XORed before the next kernel. */
 int cmx_mixnet_debug_verify_perturb(cmx_mixnet_t*, int cls, uint64_t bit, uint64_t index, uint32_t xor_mask);
+
+/* THE REDUNDANT VOTE (opt-in; src/mixnet_vote.hip). Verify mode checks what the network LOADS from HBM; what it computes with it -- the main
+ * workgroup's LDS, the layer-1 / layer-2 rows, the extras, row_steps, the SSE cells -- is covered by running the unchanged kernel on n = 2 or 3
+ * handles over the same inputs and comparing what they produce. A vote handle compares, per chunk, the n instances' final p ([nbits] f32) and mixer
+ * outputs ([nbits][47] f32) as 32-bit WORDS, never as floats: -0.0 differs from 0.0, equal NaN patterns are equal. Instance 0 is the stream's own
+ * network. Elements are ordered by e = t * 48 + c, c = 0..46 the mixer, c = 47 the final p (the causal order within a bit). n = 3: all equal agree;
+ * exactly two equal make the third the ODD instance; all different is NO MAJORITY. n = 2: different is no majority.
+ * cmx_vote_run is asynchronous on `stream` (a hipStream_t as void*): one grid-stride kernel (16-byte loads where all arrays are 16-byte aligned) and
+ * a one-wave kernel behind it that folds the chunk into the sticky DEVICE record and, for the first event, captures the bit. d_sel ([nbits][47]) and
+ * d_bits ([nbits]) are the chunk's selectors and coded bits (either may be NULL: captured as 0).
+ * The record (cmx_vote_report synchronises; cmx_vote_record is its DEVICE address, as cmx_mixnet_verify_record): [0] chunks voted, [1] bits voted,
+ * [2] n, [3] chunks with at least one non-agreeing element, then of the FIRST such chunk: [4] stream bit (stream_bit0 + t) of its smallest
+ * non-agreeing e, [5] the column c there, [6] the odd instance there or UINT64_MAX for no majority, [7] non-agreeing elements in that chunk.
+ * cmx_vote_values: the capture of that bit -- words[i * 48 + c] of instance i (n x 48 used), its 47 selectors, the coded bit. Synchronises.
+ * Out of scope: continuing on the majority after an event, and the decoder's form of the network. */
+typedef struct cmx_vote cmx_vote_t;
+cmx_vote_t* cmx_vote_create(int device, int n);
+void cmx_vote_destroy(cmx_vote_t*);
+int cmx_vote_run(cmx_vote_t*, const float* const* d_p, const float* const* d_mix, size_t nbits, uint64_t stream_bit0, const uint32_t* d_sel,
+                 const uint8_t* d_bits, void* stream);
+int cmx_vote_report(cmx_vote_t*, uint64_t out[8]);
+const unsigned long long* cmx_vote_record(cmx_vote_t*);
+int cmx_vote_values(cmx_vote_t*, uint32_t words[144], uint32_t sel[47], uint32_t* bit);
+/* Every 32-bit word of two handles' state in HBM, compared (both handles on one device; synchronises it; reads ~5.6 GB: after an event and in
+ * tests, never per chunk). Regions in order: 0 rows0 [26][10001][2112], 1 rows1 [20][10001][64], 2 rows2 [10001][64], 3 row_steps [47][10001] (two
+ * words each), 4 map_keys [47][32768], 5 map_vals, 6 s6, 7 s7, 8 x1, 9 x2, 10 the scalars n_rows[48], max_steps[48], steps, sse_j, sse_pc, sse_ffl.
+ * out[0] differing words; [1..6] the first difference in region-then-address order: region, mixer, row, word index within the row (or table),
+ * the word of a, the word of b (UINT64_MAX where a field does not apply); [7..17] the count per region; [18] bit m set: layer-0 mixer m has a
+ * differing row word; [19] the same for the layer-1 and layer-2 mixers, bit m - 26. A mixer reads its layer's inputs and the outputs of the
+ * mixers BEFORE it in its layer (predictor.cpp:395-412), and its update depends on its own output alone: an origin in mixer m leaves every mixer
+ * before m in its layer identical, and an origin in layer 1 or 2 leaves all of layer 0 identical. The lowest set bit of the two masks names
+ * the origin even a chunk after the event. */
+int cmx_mixnet_state_diff(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20]);
+/* TEST HOOK: XOR one state word (addressed as cmx_mixnet_state_diff reports it) between chunks. Synchronises the device. A data change only: no
+ * kernel stops and no wait times out. */
+int cmx_mixnet_debug_state_xor(cmx_mixnet_t*, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask);
 
 /* ------------------------------------------------------------------------
  * 2b. Stage: byte-level LSTM byte mixer = ByteMixer + Lstm + LstmLayer + its ByteModel bit
@@ -475,6 +517,22 @@ int cmx_pipeline_set_tolerance(cmx_pipeline_t*, int on);
  * _verify_report as cmx_mixnet_verify_report */
 int cmx_pipeline_set_verify(cmx_pipeline_t*, int on);
 int cmx_pipeline_verify_report(cmx_pipeline_t*, uint64_t out[8]);
+/* SHADOW MIXING NETWORKS (opt-in, k = 0 off / 1 / 2; before the first chunk): k more cmx_mixnet_t run every chunk on the slot's own layer-0 rows,
+ * selectors and bits (nothing is copied), each on a stream of its own, and a vote (cmx_vote_*; instance 0 = the stream's network) follows every
+ * chunk. Refused, with the reason, together with tolerance mode, when the device's hardware-queue budget (CMX_MAX_HW_QUEUES) does not allow k more
+ * streams, and when its compute units do not allow 27 more resident workgroups per shadow. The k handles (~2.8 GB each) and the per-slot p / mixer
+ * output buffers are created at the first cmx_pipeline_finish; with k = 0 nothing is allocated or launched. cmx_pipeline_wait / _fetch / _sync
+ * fail the chunk in which instances first disagreed -- the message names the chunk, the stream bit, the column ("mixer 31" or "final p") and the odd
+ * instance or "no majority between 2 instances" -- and void the handle, which can still be diagnosed (the calls below) and destroyed. May be
+ * combined with verify mode (which covers instance 0). A handle that decodes (cmx_pipeline_late_start) drops the reservation: its report stays at
+ * zero chunks. _shadow_report / _shadow_values: as cmx_vote_report / cmx_vote_values (all zero while nothing was voted). _shadow_state_diff:
+ * cmx_mixnet_state_diff of instances a and b (0 = the stream's own network). _debug_shadow_xor: the test hook cmx_mixnet_debug_state_xor on one
+ * instance, between chunks. */
+int cmx_pipeline_set_shadow(cmx_pipeline_t*, int k);
+int cmx_pipeline_shadow_report(cmx_pipeline_t*, uint64_t out[8]);
+int cmx_pipeline_shadow_values(cmx_pipeline_t*, uint32_t words[144], uint32_t sel[47], uint32_t* bit);
+int cmx_pipeline_shadow_state_diff(cmx_pipeline_t*, int a, int b, uint64_t out[20]);
+int cmx_pipeline_debug_shadow_xor(cmx_pipeline_t*, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask);
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t*);
 /* Predictor::Pretrain over n dictionary bytes (HOST pointer), before the first submit: only the stages holding
  * `models_` learn (today: contexts + small models); mixers, SSE, LSTM and PPMd are not trained (predictor.cpp:471-487). */

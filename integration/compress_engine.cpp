@@ -126,6 +126,9 @@ int main(int argc, char* argv[]) {
   {   // CMIX_VERIFY=1: the mixing network checks every word it consumes; a mismatch stops the program before a wrong file is written
     const char* ver = getenv("CMIX_VERIFY");
     if (ver && ver[0] == '1' && cmx_pipeline_set_verify(p.pipe(), 1)) Predictor::Die();
+    // CMIX_SHADOW=1|2: that many shadow mixing networks vote on every chunk's probabilities; a disagreement stops the program
+    const char* sha = getenv("CMIX_SHADOW");
+    if (sha && (sha[0] == '1' || sha[0] == '2') && cmx_pipeline_set_shadow(p.pipe(), sha[0] - '0')) Predictor::Die();
   }
   const double t_ready = since();
   if (enable_preprocess) preprocessor::Pretrain(&p, dictionary);

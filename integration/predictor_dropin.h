@@ -50,6 +50,9 @@ class Predictor {
     // CMIX_VERIFY=1: the mixing network checks every word it consumes; a mismatch stops the program before a wrong file is finished (a decoder is not covered)
     const char* ver = getenv("CMIX_VERIFY");
     if (ver && ver[0] == '1' && cmx_set_verify(h_, 1)) Die();
+    // CMIX_SHADOW=1|2: that many shadow mixing networks run beside the stream's own and vote on every chunk's probabilities (a decoder is not covered)
+    const char* sha = getenv("CMIX_SHADOW");
+    if (sha && (sha[0] == '1' || sha[0] == '2') && cmx_set_shadow(h_, sha[0] - '0')) Die();
   }
   ~Predictor() { cmx_destroy(h_); }
   Predictor(const Predictor&) = delete;
