@@ -572,6 +572,20 @@ int cmx_mixnet_state_view(cmx_mixnet_t* h, const MixState** host, MixState** dev
   if (device) *device = h->device;
   return 0;
 }
+// mixnet_vote.hip (cmx_mixnet_state_repair): the stored layer-0 row-segment digests of a verifying handle ([26][10001][4], cmx_verify.h), else NULL --
+// a repaired row word leaves its segment's digest stale
+unsigned long long* cmx_mixnet_verify_segments(cmx_mixnet_t* h) { return h && h->verify ? h->d_vseg : nullptr; }
+// ... and the host copy's scalars re-read from the device block after a repair wrote some of them (the pointers never change; no kernel is launched
+// from the host copy's scalars, they are kept equal to the device's so that the copy stays a true mirror)
+int cmx_mixnet_state_refresh(cmx_mixnet_t* h) {
+  if (!h || !h->d_state) { set_err("cmx_mixnet_state_refresh: null handle"); return 1; }
+  MixState t;
+  if (hipSetDevice(h->device) != hipSuccess || hipMemcpy(&t, h->d_state, sizeof t, hipMemcpyDeviceToHost) != hipSuccess) { set_err("cmx_mixnet_state_refresh: device error"); return 1; }
+  MixState& S = h->h_state;
+  memcpy(S.n_rows, t.n_rows, sizeof S.n_rows); memcpy(S.max_steps, t.max_steps, sizeof S.max_steps);
+  S.steps = t.steps; S.sse_j = t.sse_j; S.sse_pc = t.sse_pc; S.sse_ffl = t.sse_ffl;
+  return 0;
+}
 // DEVICE address of MixState::error (set by a chunk kernel whose bounded in-launch wait ran out), for callers that copy it back in
 // stream order behind the chunk's kernel (cmx_pipeline_finish) instead of synchronising the device
 const int* cmx_mixnet_error_flag(cmx_mixnet_t* h) { return h ? &h->d_state->error : nullptr; }

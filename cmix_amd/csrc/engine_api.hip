@@ -83,6 +83,8 @@ struct cmx_engine {
   bool has_dict = false;
   bool verify = false;            // cmx_set_verify: the look-ahead pipeline's mixing network runs in verify mode
   int shadow = 0;                 // cmx_set_shadow: shadow mixing networks of the look-ahead pipeline, voting on every chunk
+  int shadow_repair = 0;          // cmx_set_shadow_repair: repairs on the majority the pipeline may make (0 = off)
+  struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t mixer = 0, row = 0, index = 0; uint32_t mask = 0; } dbg_xor;   // cmx_debug_shadow_xor
   int mode = 0;                   // 0 undecided, 1 per-bit stages built (columns from the caller), 2 look-ahead pipeline built, 3 the decoder's pipeline (late-bit protocol)
   LookAhead* la = nullptr;
   cmx_pipeline_t* late = nullptr; // mode 3: every model family on the device, bits arriving one at a time (cmx_pipeline_late_*)
@@ -320,7 +322,8 @@ int ensure_lookahead(cmx_engine* h) {
   la->pipe = cmx_pipeline_create(h->vocab, h->device, kLaChunk);
   bool ok = la->pipe && cmx_pipeline_enable_fxcm(la->pipe, h->has_dict ? h->dict.c_str() : nullptr) == 0 &&
             cmx_pipeline_enable_paq8(la->pipe) == 0 && (!h->verify || cmx_pipeline_set_verify(la->pipe, 1) == 0) &&
-            (!h->shadow || cmx_pipeline_set_shadow(la->pipe, h->shadow) == 0);
+            (!h->shadow || cmx_pipeline_set_shadow(la->pipe, h->shadow) == 0) &&
+            (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0);
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
   const size_t T = 8 * kLaChunk;
   for (size_t i = 0; ok && i < kLaSlots; ++i) {
@@ -348,6 +351,10 @@ int la_top_up(cmx_engine* h, bool force_tail) {
     if (n > kLaChunk) n = kLaChunk;
     else if (n < kLaChunk && !la->ended && !force_tail) break;
     const size_t k = la->n_sub % kLaSlots;
+    if (h->dbg_xor.armed && la->n_sub == h->dbg_xor.after + 1) {   // (test hook) between chunk `after` and this one
+      h->dbg_xor.armed = false;
+      if (cmx_pipeline_debug_shadow_xor(la->pipe, h->dbg_xor.instance, h->dbg_xor.region, h->dbg_xor.mixer, h->dbg_xor.row, h->dbg_xor.index, h->dbg_xor.mask)) return 1;
+    }
     if (cmx_pipeline_submit(la->pipe, la->data.data() + (la->submitted - la->base), n, la->d_layer0[k], la->d_p[k])) return 1;
     la->ring[k].off = la->submitted;
     la->ring[k].n = n;
@@ -652,7 +659,29 @@ int cmx_set_shadow(cmx_t* h, int k) {
   if (!h) { cmx_set_err("cmx_set_shadow: null handle"); return 1; }
   if (k < 0 || k > 2) { cmx_set_err("cmx_set_shadow: k must be 0, 1 or 2 shadow mixing networks"); return 1; }
   if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  if (k != 2 && h->shadow_repair) { cmx_set_err("cmx_set_shadow: repair on the majority is set (cmx_set_shadow_repair), which needs 2 shadows"); return 1; }
   h->shadow = k;
+  return 0;
+}
+int cmx_set_shadow_repair(cmx_t* h, int max_repairs) {
+  if (!h) { cmx_set_err("cmx_set_shadow_repair: null handle"); return 1; }
+  if (max_repairs < 0) { cmx_set_err("cmx_set_shadow_repair: max_repairs must be 0 (off) or the number of repairs allowed"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_shadow_repair: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  if (max_repairs && h->shadow != 2) { cmx_set_err("cmx_set_shadow_repair: repair needs 2 shadow mixing networks (cmx_set_shadow(h, 2) first): a vote of two has no majority"); return 1; }
+  h->shadow_repair = max_repairs;
+  return 0;
+}
+int cmx_shadow_repairs(cmx_t* h, uint64_t out[], size_t cap) {
+  if (!h || !out || cap < 2) { cmx_set_err("cmx_shadow_repairs: bad argument"); return 1; }
+  if (!h->la) { out[0] = out[1] = 0; return 0; }
+  return cmx_pipeline_shadow_repairs(h->la->pipe, out, cap);
+}
+int cmx_debug_shadow_xor(cmx_t* h, uint64_t after_chunk, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
+  if (!h) { cmx_set_err("cmx_debug_shadow_xor: null handle"); return 1; }
+  if (!h->shadow) { cmx_set_err("cmx_debug_shadow_xor: no shadow mixing networks are set"); return 1; }
+  if (h->la && h->la->n_sub > after_chunk + 1) { cmx_set_err("cmx_debug_shadow_xor: that chunk has been submitted already"); return 1; }
+  h->dbg_xor.armed = true; h->dbg_xor.after = after_chunk; h->dbg_xor.instance = instance; h->dbg_xor.region = region;
+  h->dbg_xor.mixer = mixer; h->dbg_xor.row = row; h->dbg_xor.index = index; h->dbg_xor.mask = xor_mask;
   return 0;
 }
 int cmx_shadow_report(cmx_t* h, uint64_t out[8]) {

@@ -1,4 +1,5 @@
-// mixnet_vote.hip -- the redundant mixing-network vote (C ABI: cmx_vote_*, cmx_mixnet_state_diff, cmx_mixnet_debug_state_xor in include/cmix_amd.h).
+// mixnet_vote.hip -- the redundant mixing-network vote (C ABI: cmx_vote_*, cmx_mixnet_state_diff, cmx_mixnet_state_repair, cmx_mixnet_debug_state_xor in
+// include/cmix_amd.h).
 //
 // Verify mode (cmx_verify.h) checks every word the network LOADS from HBM against its source. What it cannot see is what the network computes with
 // those words: the main workgroup's LDS, the layer-1 / layer-2 rows, the extras, row_steps, the SSE cells. The complementary guard is redundancy:
@@ -7,8 +8,12 @@
 //   cmx_vote_kernel        every chunk: the final p and the 47 mixer outputs of every bit of n = 2 or 3 instances, word for word
 //   cmx_vote_fold_kernel   behind it: folds the chunk's result into a sticky record and captures the first differing bit
 //   cmx_state_diff_kernel  after an event (and in tests): every word of two handles' MixState arrays in HBM
+//   cmx_state_repair_kernel  the same walk that also stores the second handle's word over every differing word of the first: an outvoted instance
+//                          is made equal to a member of the majority (cmx_mixnet_state_repair), and cmx_verify_reseg_kernel re-digests the layer-0
+//                          row segments of a verifying handle that received such a word
 //
-// Out of scope here: continuing a stream on the majority after an event (the handle is voided, as in verify mode), and the decoder's form of the
+// Continuing a stream on the majority after an event is the pipeline's business (cmx_pipeline_set_shadow_repair, pipeline_api.hip): the fold
+// kernel publishes every chunk's own result for it (cmx_vote_last) beside the sticky record. Out of scope here: the decoder's form of the
 // network (a decoder's bits arrive one at a time from the host; its pipeline allocates nothing of this).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -18,9 +23,12 @@
 
 #include "../../include/cmix_amd.h"
 #include "mixnet_state.h"
+#include "cmx_verify.h"
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
 extern "C" int cmx_mixnet_state_view(cmx_mixnet_t* h, const MixState** host, MixState** dev, int* device);   // cmx_api.hip
+extern "C" unsigned long long* cmx_mixnet_verify_segments(cmx_mixnet_t* h);   // cmx_api.hip: a verifying handle's stored row-segment digests, else NULL
+extern "C" int cmx_mixnet_state_refresh(cmx_mixnet_t* h);                     // cmx_api.hip: the host copy of the block's scalars, from the device
 
 namespace {
 constexpr unsigned long long kNone = ~0ull;
@@ -29,9 +37,11 @@ constexpr int kCols = CMX_MIXERS + 1;   // 47 mixer outputs, then the final p: t
 // device block of a vote handle
 struct VoteDev {
   unsigned long long rec[8];     // the sticky record (cmx_vote_report)
+  unsigned long long last[4];    // the chunk folded last (cmx_vote_last), right behind the record: one copy fetches both
   unsigned long long key;        // this chunk: min over non-agreeing elements of (e << 2 | odd instance, 3 = no majority); ~0 = none
   unsigned long long cnt;        // this chunk: non-agreeing elements
-  unsigned long long pad[6];
+  unsigned long long odd;        // this chunk: bit i = instance i was the odd one of some element, bit 3 = some element had no majority
+  unsigned long long pad;
   uint32_t words[3 * kCols];     // capture of the first event's bit: instance i, column c at [i * 48 + c]
   uint32_t sel[CMX_MIXERS];
   uint32_t bit;
@@ -61,19 +71,20 @@ __global__ void __launch_bounds__(256) cmx_vote_kernel(VoteArgs a, unsigned long
   const unsigned long long mt = nmix - 4 * nq, pt = nbits - 4 * pq;
   const unsigned long long items = nq + pq + mt + pt;
   unsigned long long key = kNone, cnt = 0;
+  unsigned odd = 0;
   auto mixword = [&](unsigned long long f, uint32_t w0, uint32_t w1, uint32_t w2) {
     const unsigned r = vote_one<N>(w0, w1, w2);
     if (r) {
       const unsigned long long t = f / CMX_MIXERS, c = f - t * CMX_MIXERS;
       const unsigned long long k = ((t * kCols + c) << 2) | (r - 1);
-      key = k < key ? k : key; ++cnt;
+      key = k < key ? k : key; ++cnt; odd |= 1u << (r - 1);
     }
   };
   auto pword = [&](unsigned long long t, uint32_t w0, uint32_t w1, uint32_t w2) {
     const unsigned r = vote_one<N>(w0, w1, w2);
     if (r) {
       const unsigned long long k = ((t * kCols + CMX_MIXERS) << 2) | (r - 1);
-      key = k < key ? k : key; ++cnt;
+      key = k < key ? k : key; ++cnt; odd |= 1u << (r - 1);
     }
   };
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * blockDim.x) {
@@ -98,14 +109,17 @@ __global__ void __launch_bounds__(256) cmx_vote_kernel(VoteArgs a, unsigned long
   if (__ballot(cnt != 0) == 0) return;   // (wave-uniform) nothing differed in this wave
   for (int o = 32; o; o >>= 1) {
     const unsigned long long k2 = __shfl_xor(key, o), c2 = __shfl_xor(cnt, o);
-    key = k2 < key ? k2 : key; cnt += c2;
+    key = k2 < key ? k2 : key; cnt += c2; odd |= __shfl_xor(odd, o);
   }
-  if ((threadIdx.x & 63) == 0) { atomicMin(&d->key, key); atomicAdd(&d->cnt, cnt); }
+  if ((threadIdx.x & 63) == 0) { atomicMin(&d->key, key); atomicAdd(&d->cnt, cnt); atomicOr(&d->odd, (unsigned long long)odd); }
 }
 
-// one wave, behind the vote kernel on the same stream: the chunk's key and count into the sticky record; the first event's bit is captured
+// one wave, behind the vote kernel on the same stream: the chunk's key and count into the sticky record; the first event's bit is captured.
+// The chunk's OWN result goes into last[]: [0] its non-agreeing elements (0: the instances agree, the rest is 0), [1] the stream bit and [2] the
+// column of the first of them, [3] the odd instance -- the one instance that was odd wherever the chunk's elements did not agree -- or ~0 for no
+// majority: an element at which all differ (or n = 2), or two elements with different odd instances.
 __global__ void cmx_vote_fold_kernel(VoteArgs a, unsigned long long nbits, unsigned long long bit0, int n, const uint32_t* sel, const uint8_t* bits, VoteDev* d) {
-  const unsigned long long key = d->key, cnt = d->cnt;
+  const unsigned long long key = d->key, cnt = d->cnt, odd = d->odd;
   const bool first = cnt != 0 && d->rec[3] == 0;   // (read by every lane before lane 0 writes: one wave, the barrier below orders it)
   __syncthreads();
   const unsigned long long e = key >> 2, t = e / kCols, c = e - t * kCols;
@@ -123,13 +137,16 @@ __global__ void cmx_vote_fold_kernel(VoteArgs a, unsigned long long nbits, unsig
       d->rec[4] = bit0 + t; d->rec[5] = c; d->rec[6] = (key & 3) == 3 ? kNone : (key & 3); d->rec[7] = cnt;
       d->bit = bits && t < nbits ? bits[t] : 0u;
     }
-    d->key = kNone; d->cnt = 0;   // the next chunk starts clean
+    d->last[0] = cnt; d->last[1] = cnt ? bit0 + t : 0; d->last[2] = cnt ? c : 0;
+    d->last[3] = !cnt ? 0 : odd == 1 ? 0 : odd == 2 ? 1 : odd == 4 ? 2 : kNone;
+    d->key = kNone; d->cnt = 0; d->odd = 0;   // the next chunk starts clean
   }
 }
 
 // ---- state diff: words of two arrays; per call one region ----
 struct DiffDev {
-  unsigned long long cnt, first, mask, pad;
+  unsigned long long cnt, first, mask;
+  unsigned long long was;   // repair only: min over the repaired words of (word number << 32 | the word dst held), so the first one's old value survives
 };
 // per_mixer: words per mixer of the region (0: the region has no mixer mask)
 __global__ void __launch_bounds__(256) cmx_state_diff_kernel(const uint32_t* x, const uint32_t* y, unsigned long long n, unsigned long long per_mixer, DiffDev* d) {
@@ -157,6 +174,64 @@ __global__ void __launch_bounds__(256) cmx_state_diff_kernel(const uint32_t* x, 
     first = f2 < first ? f2 : first; cnt += c2; mask |= m2;
   }
   if ((threadIdx.x & 63) == 0) { atomicMin(&d->first, first); atomicAdd(&d->cnt, cnt); if (mask) atomicOr(&d->mask, mask); }
+}
+
+// ---- state repair: the diff's walk, storing y's word over every differing word of x (y is only read) ----
+// touched (region 0 of a verifying handle, else NULL): one flag per stored row segment of cmx_verify.h, [row number][CMX_VERIFY_SEGS], set where a word
+// the segment's digest covers was repaired. Only differing words are stored, with ordinary 4-byte vector stores: a clean pass writes nothing.
+__global__ void __launch_bounds__(256) cmx_state_repair_kernel(uint32_t* x, const uint32_t* y, unsigned long long n, unsigned long long per_mixer, DiffDev* d,
+                                                               unsigned* touched) {
+  const unsigned long long nq = n / 4, items = nq + (n - 4 * nq);
+  unsigned long long first = kNone, cnt = 0, mask = 0, was = kNone;
+  auto word = [&](unsigned long long i, uint32_t old, uint32_t w) {
+    x[i] = w;
+    ++cnt; first = i < first ? i : first;
+    const unsigned long long k = (i << 32) | old;   // (every region has fewer than 2^32 words)
+    was = k < was ? k : was;
+    if (per_mixer) mask |= 1ull << (i / per_mixer);
+    if (touched) {
+      const unsigned long long row = i / CMX_ROW0_STRIDE;
+      const unsigned idx = (unsigned)(i - row * CMX_ROW0_STRIDE);
+      if (idx < CMX_IN0) touched[row * CMX_VERIFY_SEGS + (idx < 2048 ? idx >> 9 : CMX_VERIFY_SEGS - 1)] = 1u;   // (the same value from every writer)
+    }
+  };
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * blockDim.x) {
+    if (i < nq) {
+      const uint4 u = reinterpret_cast<const uint4*>(x)[i], v = reinterpret_cast<const uint4*>(y)[i];
+      if (u.x != v.x) word(4 * i, u.x, v.x);
+      if (u.y != v.y) word(4 * i + 1, u.y, v.y);
+      if (u.z != v.z) word(4 * i + 2, u.z, v.z);
+      if (u.w != v.w) word(4 * i + 3, u.w, v.w);
+    } else {
+      const unsigned long long j = 4 * nq + (i - nq);
+      const uint32_t u = x[j], v = y[j];
+      if (u != v) word(j, u, v);
+    }
+  }
+  if (__ballot(cnt != 0) == 0) return;
+  for (int o = 32; o; o >>= 1) {
+    const unsigned long long f2 = __shfl_xor(first, o), c2 = __shfl_xor(cnt, o), m2 = __shfl_xor(mask, o), w2 = __shfl_xor(was, o);
+    first = f2 < first ? f2 : first; cnt += c2; mask |= m2; was = w2 < was ? w2 : was;
+  }
+  if ((threadIdx.x & 63) == 0) { atomicMin(&d->first, first); atomicAdd(&d->cnt, cnt); if (mask) atomicOr(&d->mask, mask); atomicMin(&d->was, was); }
+}
+
+// Verify mode's stored digests of the touched layer-0 row segments, recomputed from the repaired rows: one wave per segment, the words and the sum of
+// the network kernel's own seg_digest (mixnet_chunk.hip: helper wave w owns words [512 w, 512 w + 512), the last one also 2048..2077). A digest of 0
+// (never stored by a verified launch, not checked) stays 0.
+__global__ void __launch_bounds__(256) cmx_verify_reseg_kernel(const uint32_t* rows0, const unsigned* touched, unsigned long long* seg, unsigned nseg) {
+  const unsigned lane = threadIdx.x & 63;
+  const unsigned waves = gridDim.x * (blockDim.x >> 6);
+  for (unsigned s = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); s < nseg; s += waves) {
+    if (!touched[s] || seg[s] == 0) continue;   // (wave-uniform)
+    const unsigned row = s / CMX_VERIFY_SEGS, w = s % CMX_VERIFY_SEGS;
+    const uint32_t* r = rows0 + (unsigned long long)row * CMX_ROW0_STRIDE;
+    unsigned long long dg = 0;
+    for (unsigned k = 0; k < 8; ++k) { const unsigned i = 512 * w + 64 * k + lane; dg += cmx_vmix(CMX_VC_SEGMENT, row, i, r[i]); }
+    if (w == CMX_VERIFY_SEGS - 1 && lane < CMX_IN0 - 2048) dg += cmx_vmix(CMX_VC_SEGMENT, row, 2048 + lane, r[2048 + lane]);
+    for (int o = 32; o; o >>= 1) dg += __shfl_xor(dg, o);
+    if (lane == 0) seg[s] = dg;
+  }
 }
 
 constexpr unsigned long long kR = CMX_ROWS_PER_MIXER;
@@ -291,6 +366,16 @@ int cmx_vote_report(cmx_vote_t* v, uint64_t out[8]) {
   return 0;
 }
 
+int cmx_vote_last(cmx_vote_t* v, uint64_t out[4]) {
+  if (!v || !out) { cmx_set_err("cmx_vote_last: bad argument"); return 1; }
+  unsigned long long r[4];
+  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(r, v->d->last, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) {
+    cmx_set_err("cmx_vote_last: device error"); return 1;
+  }
+  for (int i = 0; i < 4; ++i) out[i] = r[i];
+  return 0;
+}
+
 int cmx_vote_values(cmx_vote_t* v, uint32_t words[144], uint32_t sel[47], uint32_t* bit) {
   if (!v || !words) { cmx_set_err("cmx_vote_values: bad argument"); return 1; }
   VoteDev h;
@@ -303,33 +388,51 @@ int cmx_vote_values(cmx_vote_t* v, uint32_t words[144], uint32_t sel[47], uint32
   return 0;
 }
 
-int cmx_mixnet_state_diff(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20]) {
-  if (!a || !b || !out) { cmx_set_err("cmx_mixnet_state_diff: bad argument"); return 1; }
+// cmx_mixnet_state_diff (repair == false) and cmx_mixnet_state_repair (true: b's word goes over every differing word of a) are one walk
+static int state_walk(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20], bool repair) {
+  const std::string who = repair ? "cmx_mixnet_state_repair" : "cmx_mixnet_state_diff";
+  if (!a || !b || !out) { cmx_set_err(who + ": bad argument"); return 1; }
+  if (repair && a == b) { cmx_set_err(who + ": dst and src are the same handle"); return 1; }
   const MixState *ha = nullptr, *hb = nullptr; MixState *da = nullptr, *db = nullptr; int deva = 0, devb = 0;
   if (cmx_mixnet_state_view(a, &ha, &da, &deva) || cmx_mixnet_state_view(b, &hb, &db, &devb)) return 1;
-  if (deva != devb) { cmx_set_err("cmx_mixnet_state_diff: the two handles live on different devices"); return 1; }
-  if (hipSetDevice(deva) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_mixnet_state_diff: device error"); return 1; }
+  if (deva != devb) { cmx_set_err(who + ": the two handles live on different devices"); return 1; }
+  if (hipSetDevice(deva) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err(who + ": device error"); return 1; }
   Region ra[10], rb[10];
   regions_of(*ha, ra); regions_of(*hb, rb);
   DiffDev* d = nullptr;
   DiffDev h[kRegions];
   memset(h, 0, sizeof h);
-  for (DiffDev& x : h) x.first = kNone;
+  for (DiffDev& x : h) x.first = x.was = kNone;
   bool ok = hipMalloc((void**)&d, sizeof h) == hipSuccess && hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice) == hipSuccess;
+  // a verifying dst: its stored row-segment digests must follow the repaired layer-0 rows (the next reload would raise a false alarm otherwise)
+  unsigned long long* vseg = repair ? cmx_mixnet_verify_segments(a) : nullptr;
+  unsigned* touched = nullptr;
+  const unsigned nseg = CMX_MIX0 * CMX_ROWS_PER_MIXER * CMX_VERIFY_SEGS;
+  if (ok && vseg) ok = hipMalloc((void**)&touched, (size_t)nseg * 4) == hipSuccess && hipMemset(touched, 0, (size_t)nseg * 4) == hipSuccess;
   for (int r = 0; ok && r < 10; ++r) {
     const unsigned long long items = ra[r].words / 4 + 4;
     const unsigned grid = (unsigned)(items / 256 + 1 < 4096 ? items / 256 + 1 : 4096);
-    hipLaunchKernelGGL(cmx_state_diff_kernel, dim3(grid), dim3(256), 0, 0, ra[r].p, rb[r].p, ra[r].words, ra[r].per_mixer, d + r);
+    if (repair) hipLaunchKernelGGL(cmx_state_repair_kernel, dim3(grid), dim3(256), 0, 0, (uint32_t*)ra[r].p, rb[r].p, ra[r].words, ra[r].per_mixer, d + r, r == 0 ? touched : nullptr);
+    else hipLaunchKernelGGL(cmx_state_diff_kernel, dim3(grid), dim3(256), 0, 0, ra[r].p, rb[r].p, ra[r].words, ra[r].per_mixer, d + r);
     ok = hipGetLastError() == hipSuccess;
   }
   MixState sa, sb;
   ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, d, sizeof(DiffDev) * 10, hipMemcpyDeviceToHost) == hipSuccess;
+  if (ok && touched && h[0].cnt) {   // (behind the repair kernel on the same stream)
+    hipLaunchKernelGGL(cmx_verify_reseg_kernel, dim3(2048), dim3(256), 0, 0, ra[0].p, touched, vseg, nseg);
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+  }
   ok = ok && hipMemcpy(&sa, da, sizeof sa, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(&sb, db, sizeof sb, hipMemcpyDeviceToHost) == hipSuccess;
   uint32_t wa[kScalarWords], wb[kScalarWords];
   if (ok) {
     scalar_words(sa, wa); scalar_words(sb, wb);
-    for (unsigned long long i = 0; i < kScalarWords; ++i)
-      if (wa[i] != wb[i]) { if (!h[10].cnt) h[10].first = i; h[10].cnt++; }
+    for (unsigned long long i = 0; ok && i < kScalarWords; ++i)
+      if (wa[i] != wb[i]) {
+        if (!h[10].cnt) h[10].first = i;
+        h[10].cnt++;
+        if (repair) ok = hipMemcpy((char*)da + scalar_offset(i), &wb[i], 4, hipMemcpyHostToDevice) == hipSuccess;
+      }
+    if (repair && h[10].cnt) ok = ok && cmx_mixnet_state_refresh(a) == 0;
   }
   for (int i = 0; i < 20; ++i) out[i] = 0;
   for (int i = 1; i <= 6; ++i) out[i] = kNone;
@@ -339,17 +442,23 @@ int cmx_mixnet_state_diff(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20]) {
       unsigned long long loc[3];
       locate(r, h[r].first, loc);
       uint32_t x = 0, y = 0;
-      if (r < 10) ok = hipMemcpy(&x, ra[r].p + h[r].first, 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(&y, rb[r].p + h[r].first, 4, hipMemcpyDeviceToHost) == hipSuccess;
-      else { x = wa[h[r].first]; y = wb[h[r].first]; }
+      if (r < 10) {
+        ok = hipMemcpy(&y, rb[r].p + h[r].first, 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (repair) x = (uint32_t)h[r].was;   // (dst holds src's word by now)
+        else ok = ok && hipMemcpy(&x, ra[r].p + h[r].first, 4, hipMemcpyDeviceToHost) == hipSuccess;
+      } else { x = wa[h[r].first]; y = wb[h[r].first]; }
       out[1] = (uint64_t)r; out[2] = loc[0]; out[3] = loc[1]; out[4] = loc[2]; out[5] = x; out[6] = y;
     }
   }
   out[18] = h[0].mask;
   out[19] = h[1].mask | (h[2].mask ? 1ull << CMX_MIX1 : 0);
   if (d) (void)hipFree(d);
-  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_mixnet_state_diff: device error"); return 1; }
+  if (touched) (void)hipFree(touched);
+  if (!ok) { (void)hipGetLastError(); cmx_set_err(who + ": device error"); return 1; }
   return 0;
 }
+int cmx_mixnet_state_diff(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20]) { return state_walk(a, b, out, false); }
+int cmx_mixnet_state_repair(cmx_mixnet_t* dst, cmx_mixnet_t* src, uint64_t out[20]) { return state_walk(dst, src, out, true); }
 
 int cmx_mixnet_debug_state_xor(cmx_mixnet_t* net, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
   if (!net) { cmx_set_err("cmx_mixnet_debug_state_xor: null handle"); return 1; }

@@ -129,7 +129,8 @@ struct Slot {
   // shadow mixing networks (cmx_pipeline_set_shadow): allocated at the first finish, nothing of it otherwise
   float* d_shp[2] = {nullptr, nullptr};               // [8 max] p of shadow i + 1
   float* d_shmix[3] = {nullptr, nullptr, nullptr};    // [8 max][47] mixer outputs of instance i (0: the stream's own network, unless cmx_pipeline_debug_mix_out supplies the area)
-  unsigned long long* h_vote = nullptr;               // pinned [8] the vote's record as it stood behind this chunk, then [2] the shadows' sticky hand-off flags
+  unsigned long long* h_vote = nullptr;               // pinned [8] the vote's record as it stood behind this chunk, [4] the chunk's own result (cmx_vote_last), then the shadows' two sticky hand-off flags
+  float* d_mix0 = nullptr;                             // where instance 0 wrote this chunk's mixer outputs (d_shmix[0] or the debug area)
   hipEvent_t ev_sh[2] = {nullptr, nullptr}, ev_vote = nullptr;
   bool voted = false;                                  // this slot's chunk has a vote behind it: whoever waits for ev_mix1 also waits for ev_vote
 };
@@ -218,6 +219,12 @@ struct cmx_pipeline {
   cmx_mixnet_t* sh[2] = {nullptr, nullptr};   // created at the first finish
   cmx_vote_t* vote = nullptr;
   uint64_t vote_bits = 0;        // stream bits handed to the vote so far
+  // repair on the majority (cmx_pipeline_set_shadow_repair; 0 = off: wait / sync are the code without it)
+  int repair_max = 0;
+  uint64_t repairs = 0;          // repairs made
+  uint64_t repaired_events = 0;  // chunks with a non-agreeing vote that those repairs covered (the vote's sticky record goes on counting them: [3])
+  uint64_t repaired_upto = 0;    // chunks below this index had left the instances when the last repair was made
+  uint64_t repair_log[CMX_REPAIR_LOG][CMX_REPAIR_WORDS] = {};   // ring of the last repairs, entry number r at [r % CMX_REPAIR_LOG]
   float* dbg_mix = nullptr;      // diagnosis (cmx_pipeline_debug_mix_out): the 47 mixer outputs of every bit, [bit][47], as far as dbg_mix_cap bits
   uint64_t dbg_mix_cap = 0, dbg_mix_bits = 0;
 };
@@ -262,6 +269,23 @@ static std::string vote_text(const unsigned long long r[8]) {
   if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
   else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own network)" : "");
   return s + " (the stream's output is void)";
+}
+static std::string origin_text(uint64_t m0, uint64_t m12) {
+  for (int i = 0; i < 26; ++i) if (m0 >> i & 1) return "mixer " + std::to_string(i);
+  for (int i = 0; i < 21; ++i) if (m12 >> i & 1) return "mixer " + std::to_string(26 + i);
+  return "no mixer row (tables / scalars only)";
+}
+// one entry of the repair log (cmx_pipeline_shadow_repairs) in words
+static std::string repair_entry_text(const uint64_t* e) {
+  return "chunk " + std::to_string(e[0]) + ", stream bit " + std::to_string(e[1]) + ", " + (e[2] < 47 ? "mixer " + std::to_string(e[2]) : std::string("final p")) + ", instance " +
+         std::to_string(e[3]) + " odd, " + std::to_string(e[5]) + " state word(s) repaired, origin " + origin_text(e[12], e[13]);
+}
+// the repairs made so far, for the message of a stop behind them
+static std::string repairs_text(const cmx_pipeline* h) {
+  if (!h->repairs) return "";
+  std::string s = "; " + std::to_string(h->repairs) + " repair(s) on the majority before it:";
+  for (uint64_t r = h->repairs > CMX_REPAIR_LOG ? h->repairs - CMX_REPAIR_LOG : 0; r < h->repairs; ++r) s += " [" + repair_entry_text(h->repair_log[r % CMX_REPAIR_LOG]) + "]";
+  return s;
 }
 
 __global__ void cmx_fxcm_hints_kernel(const float* layer0, long stride, const float* p_after, const int* ex, int T, int16_t* lstmpr, uint8_t* lstmex) {
@@ -574,8 +598,8 @@ static int shadow_build(cmx_pipeline* h) {
   for (Slot& s : h->slot) {
     for (int i = 0; i < h->shadow; ++i) ok = ok && hipMalloc((void**)&s.d_shp[i], T * 4) == hipSuccess && hipEventCreateWithFlags(&s.ev_sh[i], hipEventDisableTiming) == hipSuccess;
     for (int i = 0; i <= h->shadow; ++i) ok = ok && hipMalloc((void**)&s.d_shmix[i], T * CMX_N_MIXERS * 4) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_vote, 10 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_vote, hipEventDisableTiming) == hipSuccess;
-    if (ok) memset(s.h_vote, 0, 10 * 8);
+    ok = ok && hipHostMalloc((void**)&s.h_vote, 14 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_vote, hipEventDisableTiming) == hipSuccess;
+    if (ok) memset(s.h_vote, 0, 14 * 8);
   }
   if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_finish: buffer allocation for the shadow mixing networks failed"); return 1; }
   return 0;
@@ -793,7 +817,7 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
       if (h->p8) (void)hipStreamWaitEvent(q, s.ev_p81, 0);
       if (cols) (void)hipStreamWaitEvent(q, s.ev_cols, 0);
       if (cmx_mixnet_run(h->sh[i], s.d_layer0, s.d_sel, s.d_bits, 8 * n, s.d_shp[i], s.d_shmix[i + 1], q)) return 1;
-      (void)hipMemcpyAsync((unsigned*)(s.h_vote + 8) + i, cmx_mixnet_error_flag(h->sh[i]), 4, hipMemcpyDeviceToHost, q);
+      (void)hipMemcpyAsync((unsigned*)(s.h_vote + 12) + i, cmx_mixnet_error_flag(h->sh[i]), 4, hipMemcpyDeviceToHost, q);
       (void)hipEventRecord(s.ev_sh[i], q);
       vp[i + 1] = s.d_shp[i]; vm[i + 1] = s.d_shmix[i + 1];
     }
@@ -801,12 +825,13 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
     (void)hipStreamWaitEvent(q, s.ev_mix1, 0);
     for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_sh[i], 0);
     if (cmx_vote_run(h->vote, vp, vm, 8 * n, h->vote_bits, s.d_sel, s.d_bits, q)) return 1;
-    (void)hipMemcpyAsync(s.h_vote, cmx_vote_record(h->vote), 64, hipMemcpyDeviceToHost, q);
+    (void)hipMemcpyAsync(s.h_vote, cmx_vote_record(h->vote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
     (void)hipEventRecord(s.ev_vote, q);
     s.voted = true;
     h->vote_bits += 8 * n;
   }
   s.d_p = d_p_out;
+  s.d_mix0 = dmix;
   h->host_ms[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fin).count();
   s.untimed = true;
   h->last_slot = (int)(h->finished % kSlots);
@@ -884,6 +909,97 @@ int cmx_pipeline_pretrain(cmx_pipeline_t* h, const uint8_t* bytes, size_t n) {
   return 0;
 }
 
+// ---- repair on the majority (include/cmix_amd.h, cmx_pipeline_set_shadow_repair) ----
+int cmx_pipeline_set_shadow_repair(cmx_pipeline_t* h, int max_repairs) {
+  if (!h) { cmx_set_err("cmx_pipeline_set_shadow_repair: null handle"); return 1; }
+  if (max_repairs < 0) { cmx_set_err("cmx_pipeline_set_shadow_repair: max_repairs must be 0 (off) or the number of repairs allowed"); return 1; }
+  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_shadow_repair: only before the first chunk"); return 1; }
+  if (max_repairs && h->shadow != 2) {
+    cmx_set_err("cmx_pipeline_set_shadow_repair: repair needs 2 shadow mixing networks (cmx_pipeline_set_shadow(2) first): a vote of " + std::to_string(1 + h->shadow) +
+                " instance(s) has no majority to continue on");
+    return 1;
+  }
+  h->repair_max = max_repairs;
+  return 0;
+}
+const char* cmx_repair_text(const uint64_t entry[CMX_REPAIR_WORDS]) {
+  static thread_local std::string s;
+  s = entry ? repair_entry_text(entry) : std::string();
+  return s.c_str();
+}
+int cmx_pipeline_shadow_repairs(cmx_pipeline_t* h, uint64_t out[], size_t cap) {
+  if (!h || !out || cap < 2) { cmx_set_err("cmx_pipeline_shadow_repairs: bad argument (out holds 2 words, then CMX_REPAIR_WORDS per entry)"); return 1; }
+  const uint64_t have = h->repairs < CMX_REPAIR_LOG ? h->repairs : CMX_REPAIR_LOG, room = (cap - 2) / CMX_REPAIR_WORDS;
+  const uint64_t n = have < room ? have : room;   // the newest n, oldest first
+  out[0] = h->repairs; out[1] = n;
+  for (uint64_t i = 0; i < n; ++i) memcpy(out + 2 + i * CMX_REPAIR_WORDS, h->repair_log[(h->repairs - n + i) % CMX_REPAIR_LOG], CMX_REPAIR_WORDS * 8);
+  return 0;
+}
+// cmx_pipeline_wait(index) found events beyond those repaired. Drains the instances, decides between repair and stop over every chunk they have run
+// since the last repair (the rule's specification is cmix_amd/vote.py::repair_decision), repairs the odd instance's state from a member of the
+// majority and, where the odd instance is the stream's own network, replaces the outputs of the chunks it ran past the event. 0: repaired.
+static int shadow_repair(cmx_pipeline* h, uint64_t index) {
+  const Slot& sw = h->slot[index % kSlots];
+  auto stop = [&](const unsigned long long* event) {   // today's message (the sticky record), the repairs before it, and -- where it is not the record's -- this event
+    std::string m = "cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + vote_text(sw.h_vote) + repairs_text(h);
+    if (h->repairs && event)
+      m += "; not repaired: stream bit " + std::to_string(event[1]) + ", " + (event[2] < 47 ? "mixer " + std::to_string(event[2]) : std::string("final p")) + ", " +
+           (event[3] == ~0ull ? std::string("no majority") : "instance " + std::to_string(event[3]) + " odd");
+    cmx_set_err(m);
+    h->failed = true;
+    return 1;
+  };
+  // 1. drain: look-ahead keeps up to kSlots chunks in flight, the instances have run past the event
+  const uint64_t lo0 = h->finished > (uint64_t)kSlots ? h->finished - kSlots : 0, lo = lo0 > h->repaired_upto ? lo0 : h->repaired_upto;
+  bool ok = true;
+  for (uint64_t c = lo; c < h->finished; ++c) ok = slot_done(h->slot[c % kSlots]) == hipSuccess && ok;
+  ok = hipStreamSynchronize(h->s_mix) == hipSuccess && ok;
+  for (hipStream_t q : h->s_sh) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
+  if (!ok) { cmx_set_err("cmx_pipeline_wait: device error while draining for a repair"); h->failed = true; return 1; }
+  // 2. / 3. every chunk in flight: agree, or the same odd instance; no time-out of a shadow; the sticky count accounted for; budget left
+  uint64_t odd = ~0ull, first = ~0ull, events = 0;
+  for (uint64_t c = lo; c < h->finished; ++c) {
+    const Slot& s = h->slot[c % kSlots];
+    const unsigned* shfail = (const unsigned*)(s.h_vote + 12);
+    const unsigned long long* last = s.h_vote + 8;
+    if (!s.voted || shfail[0] || shfail[1]) return stop(nullptr);
+    if (!last[0]) continue;
+    if (last[3] == ~0ull || (odd != ~0ull && last[3] != odd)) return stop(last);
+    if (first == ~0ull) { first = c; odd = last[3]; }
+    ++events;
+  }
+  const Slot& newest = h->slot[(h->finished - 1) % kSlots];
+  if (first == ~0ull || newest.h_vote[3] != h->repaired_events + events) return stop(nullptr);   // an event in a chunk whose slot has been reused: its result is gone
+  const unsigned long long* ev = h->slot[first % kSlots].h_vote + 8;
+  if (h->repairs >= (uint64_t)h->repair_max) return stop(ev);
+  // 4. the odd instance's state from a member of the majority
+  cmx_mixnet_t* inst[3] = {h->mix, h->sh[0], h->sh[1]};
+  uint64_t out[20];
+  if (cmx_mixnet_state_repair(inst[odd], inst[odd == 0 ? 1 : 0], out)) { h->failed = true; return 1; }
+  // 5. the stream's own network was the odd one: the caller's p (and the debug area's mixer outputs) of every chunk it got wrong, from shadow 1.
+  //    Nothing else on the device reads the final p: the stages' hints come from the LSTM's column of the layer-0 rows.
+  if (odd == 0) {
+    for (uint64_t c = lo; ok && c < h->finished; ++c) {
+      const Slot& s = h->slot[c % kSlots];
+      if (!s.h_vote[8]) continue;
+      ok = hipMemcpy(s.d_p, s.d_shp[0], 8 * s.n * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess;
+      if (ok && s.d_mix0 != s.d_shmix[0]) ok = hipMemcpy(s.d_mix0, s.d_shmix[1], 8 * s.n * 47 * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess;
+    }
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { cmx_set_err("cmx_pipeline_wait: device error while replacing the outvoted network's outputs"); h->failed = true; return 1; }
+  }
+  // 6. the log
+  uint64_t* e = h->repair_log[h->repairs % CMX_REPAIR_LOG];
+  memset(e, 0, CMX_REPAIR_WORDS * 8);
+  e[0] = first; e[1] = ev[1]; e[2] = ev[2]; e[3] = odd; e[4] = ev[0]; e[5] = out[0];
+  for (int i = 1; i <= 6; ++i) e[5 + i] = out[i];
+  e[12] = out[18]; e[13] = out[19]; e[14] = events;
+  h->repairs++;
+  h->repaired_events += events;
+  h->repaired_upto = h->finished;
+  return 0;
+}
+
 // Wait until chunk number `index` (0 = the first chunk submitted) has left the mixing network: its p[] is complete.
 // Only the last CMX_PIPELINE_SLOTS chunks can be waited for (their slots still hold the events). Also reports a timed-out
 // in-launch hand-off of the multi-workgroup LSTM / fxcm kernels as of this chunk (their sticky flags were copied back in
@@ -908,14 +1024,16 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
     return 1;
   }
   if (s.voted) {
-    const unsigned* shfail = (const unsigned*)(s.h_vote + 8);
+    const unsigned* shfail = (const unsigned*)(s.h_vote + 12);
     if (shfail[0] || shfail[1]) {
       cmx_set_err("cmx_pipeline_wait: an in-launch hand-off of shadow mixing network " + std::to_string(shfail[0] ? 1 : 2) + " timed out (workgroups not co-resident?): the vote is void from chunk " +
                   std::to_string(index) + " on");
       h->failed = true;
       return 1;
     }
-    if (s.h_vote[3]) {   // the instances disagreed in this chunk or an earlier one (the record is sticky)
+    if (h->repair_max) {   // events beyond those repaired (chunks that an earlier repair drained have their output from the majority already)
+      if (index >= h->repaired_upto && s.h_vote[3] > h->repaired_events && shadow_repair(h, index)) return 1;
+    } else if (s.h_vote[3]) {   // the instances disagreed in this chunk or an earlier one (the record is sticky)
       cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + vote_text(s.h_vote));
       h->failed = true;
       return 1;
@@ -954,7 +1072,7 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
   if (h->vote) {
     uint64_t r[8];
     if (cmx_vote_report(h->vote, r)) { h->failed = true; return 1; }
-    if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + vote_text(t)); h->failed = true; return 1; }
+    if (r[3] > h->repaired_events) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + vote_text(t) + repairs_text(h)); h->failed = true; return 1; }
   }
   // the multi-workgroup kernels bound every in-launch wait: one that ran out left garbage behind, not a hang
   if (cmx_lstm_failed(h->lstm)) { cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the LSTM kernels timed out (workgroups not co-resident?): the stream's output is void"); h->failed = true; return 1; }

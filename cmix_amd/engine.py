@@ -180,6 +180,15 @@ def lib():
         L.cmx_pipeline_debug_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
         L.cmx_set_shadow.argtypes = [C.c_void_p, C.c_int]
         L.cmx_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_vote_last.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_mixnet_state_repair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_set_shadow_repair.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_pipeline_shadow_repairs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_set_shadow_repair.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_shadow_repairs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_repair_text.restype = C.c_char_p
+        L.cmx_repair_text.argtypes = [C.c_void_p]
+        L.cmx_debug_shadow_xor.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
         L.cmx_pipeline_late_start.argtypes = [C.c_void_p, C.c_int]
         L.cmx_pipeline_late_predict.restype = C.c_float
         L.cmx_pipeline_late_predict.argtypes = [C.c_void_p]
@@ -260,6 +269,25 @@ def _u64(v):
     return _NONE64 if v is None else int(v)
 
 
+REPAIR_LOG, REPAIR_WORDS = 8, 16   # CMX_REPAIR_LOG, CMX_REPAIR_WORDS (include/cmix_amd.h)
+
+
+def _shadow_repairs(fn, h):
+    """cmx_pipeline_shadow_repairs / cmx_shadow_repairs as a dict: total, and log = the newest (at most 8) repairs, oldest first"""
+    out = (C.c_uint64 * (2 + REPAIR_LOG * REPAIR_WORDS))()
+    if fn(h, out, len(out)):
+        raise CmxError(last_error())
+    v = [int(x) for x in out]
+    log = []
+    for i in range(v[1]):
+        e = v[2 + i * REPAIR_WORDS:2 + (i + 1) * REPAIR_WORDS]
+        first = {"region": e[6], "mixer": _opt(e[7]), "row": _opt(e[8]), "index": _opt(e[9]), "a": e[10], "b": e[11]} if e[5] else None
+        text = lib().cmx_repair_text((C.c_uint64 * REPAIR_WORDS)(*e)).decode()
+        log.append({"text": text, "chunk": e[0], "bit": e[1], "column": e[2], "odd": e[3], "elements": e[4], "words": e[5], "first": first,
+                    "layer0_mask": e[12], "layer12_mask": e[13], "chunks": e[14], "raw": e})
+    return {"total": v[0], "log": log}
+
+
 def _region(r):
     return STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
 
@@ -293,6 +321,16 @@ class Vote:
         """dict: chunks, bits, n, events (chunks with a non-agreeing element), and of the first event: first_bit, column (0..46 mixer, 47 final p),
         odd (instance, None = no majority), elements; raw = the eight words. Synchronises the device."""
         return _vote_report(lib().cmx_vote_report, self.h)
+
+    def last(self):
+        """the chunk voted last alone (cmx_vote_last): dict elements (0 = the instances agreed), bit, column, odd (None = no majority; bit, column
+        and odd are None without an event), raw = the four words. Synchronises the device."""
+        out = (C.c_uint64 * 4)()
+        if lib().cmx_vote_last(self.h, out):
+            raise CmxError(last_error())
+        v = [int(x) for x in out]
+        ev = v[0] != 0
+        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
 
     def values(self):
         """the captured bit of the first event: words [n, 48] u32, sel [47] u32, bit"""
@@ -354,6 +392,14 @@ class MixNet:
         (region, mixer, row, index, a, b -- None where a field does not apply), per_region, layer0_mask, layer12_mask, raw. Synchronises the device."""
         out = (C.c_uint64 * 20)()
         if lib().cmx_mixnet_state_diff(self.h, other.h, out):
+            raise CmxError(last_error())
+        return _state_diff(out)
+
+    def state_repair(self, src):
+        """Every state word of this handle that differs from `src`'s overwritten with src's (include/cmix_amd.h, cmx_mixnet_state_repair); returns
+        what state_diff(src) would have returned just before. Between chunks; synchronises the device."""
+        out = (C.c_uint64 * 20)()
+        if lib().cmx_mixnet_state_repair(self.h, src.h, out):
             raise CmxError(last_error())
         return _state_diff(out)
 
@@ -745,6 +791,16 @@ class Pipeline:
             raise CmxError(last_error())
         self._shadow = int(k)
 
+    def set_shadow_repair(self, max_repairs):
+        """Repair on the majority (include/cmix_amd.h, cmx_pipeline_set_shadow_repair): after set_shadow(2), before the first chunk; wait / fetch
+        then repair the outvoted instance from the majority, up to max_repairs times, instead of failing the chunk. 0 = off."""
+        if lib().cmx_pipeline_set_shadow_repair(self.h, int(max_repairs)):
+            raise CmxError(last_error())
+
+    def shadow_repairs(self):
+        """dict total, log (the newest repairs, oldest first: chunk, bit, column, odd, elements, words, first, layer0_mask, layer12_mask, chunks)"""
+        return _shadow_repairs(lib().cmx_pipeline_shadow_repairs, self.h)
+
     def shadow_report(self):
         """as Vote.report (all zero while nothing was voted)"""
         return _vote_report(lib().cmx_pipeline_shadow_report, self.h)
@@ -1021,6 +1077,20 @@ class Predictor:
     def set_shadow(self, k):
         """Shadow mixing networks of the look-ahead pipeline (include/cmix_amd.h, cmx_set_shadow): before the first stage_input / Predict."""
         if lib().cmx_set_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+
+    def set_shadow_repair(self, max_repairs):
+        """Repair on the majority (include/cmix_amd.h, cmx_set_shadow_repair): after set_shadow(2), before the first stage_input / Predict."""
+        if lib().cmx_set_shadow_repair(self.h, int(max_repairs)):
+            raise CmxError(last_error())
+
+    def shadow_repairs(self):
+        """as Pipeline.shadow_repairs (empty unless the handle compresses)"""
+        return _shadow_repairs(lib().cmx_shadow_repairs, self.h)
+
+    def debug_shadow_xor(self, after_chunk, instance, region, mixer, row, index, xor_mask):
+        """Test hook: one Pipeline.debug_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""
+        if lib().cmx_debug_shadow_xor(self.h, int(after_chunk), int(instance), _region(region), _u64(mixer), _u64(row), _u64(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def shadow_report(self):

@@ -59,7 +59,7 @@ class EngineStream:
     is for a compressor (reference src/predictor.cpp:361-469), a sub-chunk of known bytes at a time. feed() enqueues;
     finish() returns the container bytes (header + arithmetic code), identical to the reference binary's file."""
 
-    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0):
+    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0, repair=0):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", device_index)
@@ -82,6 +82,10 @@ class EngineStream:
             self.pipe.set_verify(True)
         if shadow:   # that many shadow mixing networks vote on every sub-chunk's probabilities (cmx_pipeline_set_shadow): finish() raises on a disagreement
             self.pipe.set_shadow(shadow)
+        self.repair = int(repair)
+        if self.repair:   # up to that many repairs on the majority (cmx_pipeline_set_shadow_repair, shadow=2 only): every sub-chunk is then waited for before its slot is reused
+            self.pipe.set_shadow_repair(self.repair)
+        self.waited = 0
         self.pos = 0
         self.nsub = 0
         torch.cuda.synchronize(self.dev)
@@ -91,6 +95,9 @@ class EngineStream:
         end = min(self.pos + nbytes, len(self.stream))
         while self.pos < end:
             m = min(self.sub, end - self.pos)
+            if self.repair and self.nsub >= E.PIPELINE_SLOTS:   # the sub-chunk whose slot this one takes (the submit would wait for it anyway): an event in it is repaired here
+                self.pipe.wait(self.nsub - E.PIPELINE_SLOTS)
+                self.waited = self.nsub - E.PIPELINE_SLOTS + 1
             l0 = self.layer0[self.nsub % E.PIPELINE_SLOTS][:8 * m]
             self.pipe.submit(self.stream[self.pos:self.pos + m], l0, self.p_dev[8 * self.pos:8 * (self.pos + m)])
             self.pos += m
@@ -98,6 +105,10 @@ class EngineStream:
 
     def finish(self):
         """Wait for the device, bring p[] back, run the arithmetic coder (host: a multiply-add and a compare per bit)."""
+        if self.repair:
+            for i in range(self.waited, self.nsub):
+                self.pipe.wait(i)
+            self.waited = self.nsub
         self.pipe.sync()
         p = self.p_dev[:8 * self.pos].cpu().numpy()
         enc = E.Encoder()

@@ -107,9 +107,17 @@ int cmx_verify_report(cmx_t*, uint64_t out[8]);
 /* Shadow mixing networks of the look-ahead pipeline (cmx_pipeline_set_shadow, k = 0 / 1 / 2): before the first cmx_stage_input or cmx_predict.
  * cmx_predict then returns < 0 instead of a probability of a chunk in which the instances disagreed. A handle that decodes is not covered: its
  * report stays at zero chunks. The programs in integration/ read CMIX_SHADOW=1|2; the library reads no environment variable for it.
- * cmx_shadow_report: as cmx_vote_report. */
+ * cmx_shadow_report: as cmx_vote_report.
+ * cmx_set_shadow_repair(max_repairs): repair on the majority (cmx_pipeline_set_shadow_repair, which states what a repaired stream guarantees);
+ * 0 = off, the default; > 0 after cmx_set_shadow(h, 2) only. cmx_shadow_repairs: as cmx_pipeline_shadow_repairs (two zero words before the
+ * pipeline exists). The programs in integration/ read CMIX_SHADOW_REPAIR=N (with CMIX_SHADOW=2 only) and print one line per repair at the end.
+ * TEST HOOK cmx_debug_shadow_xor: arms ONE cmx_pipeline_debug_shadow_xor(instance, region, mixer, row, index, xor_mask), made between chunk
+ * `after_chunk` and the next one of the look-ahead stream (chunks of 4096 bytes, 0 = the first). */
 int cmx_set_shadow(cmx_t*, int k);
 int cmx_shadow_report(cmx_t*, uint64_t out[8]);
+int cmx_set_shadow_repair(cmx_t*, int max_repairs);
+int cmx_shadow_repairs(cmx_t*, uint64_t out[], size_t cap);
+int cmx_debug_shadow_xor(cmx_t*, uint64_t after_chunk, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask);
 void cmx_destroy(cmx_t*);
 
 /* ------------------------------------------------------------------------
@@ -218,7 +226,11 @@ int cmx_mixnet_debug_verify_perturb(cmx_mixnet_t*, int cls, uint64_t bit, uint64
  * [2] n, [3] chunks with at least one non-agreeing element, then of the FIRST such chunk: [4] stream bit (stream_bit0 + t) of its smallest
  * non-agreeing e, [5] the column c there, [6] the odd instance there or UINT64_MAX for no majority, [7] non-agreeing elements in that chunk.
  * cmx_vote_values: the capture of that bit -- words[i * 48 + c] of instance i (n x 48 used), its 47 selectors, the coded bit. Synchronises.
- * Out of scope: continuing on the majority after an event, and the decoder's form of the network. */
+ * cmx_vote_last: the result of the chunk voted LAST alone (synchronises; on the device it lies right behind the record: cmx_vote_record + 8):
+ * [0] its non-agreeing elements (0: the instances agreed, [1..3] are 0), [1] the stream bit and [2] the column of the first of them, [3] the
+ * chunk's odd instance -- the one instance that was odd at every non-agreeing element -- or UINT64_MAX for no majority (an element at which all
+ * differ, n = 2, or elements with different odd instances).
+ * Continuing on the majority after an event is cmx_pipeline_set_shadow_repair's; out of scope: the decoder's form of the network. */
 typedef struct cmx_vote cmx_vote_t;
 cmx_vote_t* cmx_vote_create(int device, int n);
 void cmx_vote_destroy(cmx_vote_t*);
@@ -227,6 +239,7 @@ int cmx_vote_run(cmx_vote_t*, const float* const* d_p, const float* const* d_mix
 int cmx_vote_report(cmx_vote_t*, uint64_t out[8]);
 const unsigned long long* cmx_vote_record(cmx_vote_t*);
 int cmx_vote_values(cmx_vote_t*, uint32_t words[144], uint32_t sel[47], uint32_t* bit);
+int cmx_vote_last(cmx_vote_t*, uint64_t out[4]);
 /* Every 32-bit word of two handles' state in HBM, compared (both handles on one device; synchronises it; reads ~5.6 GB: after an event and in
  * tests, never per chunk). Regions in order: 0 rows0 [26][10001][2112], 1 rows1 [20][10001][64], 2 rows2 [10001][64], 3 row_steps [47][10001] (two
  * words each), 4 map_keys [47][32768], 5 map_vals, 6 s6, 7 s7, 8 x1, 9 x2, 10 the scalars n_rows[48], max_steps[48], steps, sse_j, sse_pc, sse_ffl.
@@ -237,6 +250,13 @@ int cmx_vote_values(cmx_vote_t*, uint32_t words[144], uint32_t sel[47], uint32_t
  * before m in its layer identical, and an origin in layer 1 or 2 leaves all of layer 0 identical. The lowest set bit of the two masks names
  * the origin even a chunk after the event. */
 int cmx_mixnet_state_diff(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20]);
+/* The same walk that REPAIRS: wherever a state word of dst differs from src's, src's word is stored over it (only those words are stored: the pass
+ * stays read-bound, and src is never written); the differing scalars of region 10 likewise, inside dst's device block. out[20] has exactly
+ * cmx_mixnet_state_diff(dst, src)'s layout and describes the state BEFORE the repair -- one pass diagnoses and repairs; afterwards
+ * cmx_mixnet_state_diff(dst, src) reports zero. If dst is in verify mode, the stored digests of the layer-0 row segments that received a word are
+ * recomputed from the repaired rows (they are no state region; a stale one would raise a false alarm at the row's next reload). Between chunks
+ * only; synchronises the device. Refuses dst == src and handles on different devices. */
+int cmx_mixnet_state_repair(cmx_mixnet_t* dst, cmx_mixnet_t* src, uint64_t out[20]);
 /* TEST HOOK: XOR one state word (addressed as cmx_mixnet_state_diff reports it) between chunks. Synchronises the device. A data change only: no
  * kernel stops and no wait times out. */
 int cmx_mixnet_debug_state_xor(cmx_mixnet_t*, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask);
@@ -523,7 +543,7 @@ int cmx_pipeline_verify_report(cmx_pipeline_t*, uint64_t out[8]);
  * streams, and when its compute units do not allow 27 more resident workgroups per shadow. The k handles (~2.8 GB each) and the per-slot p / mixer
  * output buffers are created at the first cmx_pipeline_finish; with k = 0 nothing is allocated or launched. cmx_pipeline_wait / _fetch / _sync
  * fail the chunk in which instances first disagreed -- the message names the chunk, the stream bit, the column ("mixer 31" or "final p") and the odd
- * instance or "no majority between 2 instances" -- and void the handle, which can still be diagnosed (the calls below) and destroyed. May be
+ * instance or "no majority between 2 instances" -- and void the handle (unless repair is armed, below), which can still be diagnosed and destroyed. May be
  * combined with verify mode (which covers instance 0). A handle that decodes (cmx_pipeline_late_start) drops the reservation: its report stays at
  * zero chunks. _shadow_report / _shadow_values: as cmx_vote_report / cmx_vote_values (all zero while nothing was voted). _shadow_state_diff:
  * cmx_mixnet_state_diff of instances a and b (0 = the stream's own network). _debug_shadow_xor: the test hook cmx_mixnet_debug_state_xor on one
@@ -533,6 +553,31 @@ int cmx_pipeline_shadow_report(cmx_pipeline_t*, uint64_t out[8]);
 int cmx_pipeline_shadow_values(cmx_pipeline_t*, uint32_t words[144], uint32_t sel[47], uint32_t* bit);
 int cmx_pipeline_shadow_state_diff(cmx_pipeline_t*, int a, int b, uint64_t out[20]);
 int cmx_pipeline_debug_shadow_xor(cmx_pipeline_t*, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask);
+/* REPAIR ON THE MAJORITY (opt-in; max_repairs = 0 off, the default: everything above holds word for word, nothing more is allocated or launched).
+ * > 0 needs k = 2 shadows (a vote of two has no majority) and, like _set_shadow, comes before the first chunk. cmx_pipeline_wait / _fetch that find
+ * an event beyond those already repaired then (1) drain every finished chunk from the three instances and the vote -- look-ahead has let them run up
+ * to CMX_PIPELINE_SLOTS chunks past the event --; (2) look at every drained chunk's own result (cmx_vote_last): each must agree or name the SAME odd
+ * instance o; (3) STOP exactly as without repair -- the same message, with the repairs made so far appended -- on no majority in any of them, a second
+ * odd instance, a shadow's time-out flag, an event whose chunk has already left its slot unseen, or max_repairs used up; otherwise (4) run
+ * cmx_mixnet_state_repair(instance o, a member of the majority); (5) if o == 0, overwrite the caller's p[] of every drained chunk that did not agree
+ * (and its part of a cmx_pipeline_debug_mix_out area) device-to-device with shadow 1's, before the call returns -- nothing else on the device
+ * consumes the final p: the stages' hints come from the LSTM's column of the layer-0 rows --; (6) log the repair and return 0: the handle stays
+ * usable. A caller that wants repair waits for (or fetches) every chunk before its slot is reused. The sticky record (_shadow_report) goes on
+ * counting events; cmx_pipeline_sync fails on events beyond those repaired.
+ * WHAT A REPAIRED STREAM GUARANTEES: its probabilities are the majority's -- two instances with independent state (rows, tables, LDS, registers)
+ * agreed on every one of the 48 words of every bit of every chunk, and after a repair all three states are equal word for word. Nothing is claimed
+ * about inputs all three share (the layer-0 rows, selectors, bits): that is verify mode's ground, and the two combine.
+ * _shadow_repairs: out[0] repairs made, out[1] the n entries that follow (the newest, at most CMX_REPAIR_LOG and what cap words hold), oldest first,
+ * CMX_REPAIR_WORDS each: [0] chunk of the event, [1] its stream bit, [2] column, [3] odd instance, [4] non-agreeing values in that chunk, [5] state
+ * words repaired (the repair's out[0]), [6..11] its out[1..6] (the first differing word), [12] out[18], [13] out[19] (the layer masks, whose lowest
+ * bit names the origin mixer), [14] drained chunks that did not agree, [15] 0. */
+#define CMX_REPAIR_LOG 8
+#define CMX_REPAIR_WORDS 16
+int cmx_pipeline_set_shadow_repair(cmx_pipeline_t*, int max_repairs);
+int cmx_pipeline_shadow_repairs(cmx_pipeline_t*, uint64_t out[], size_t cap);
+/* one entry of that log in words ("chunk 3, stream bit 6144, mixer 26, instance 0 odd, 812 state word(s) repaired, origin mixer 26"): a
+ * thread-local string, valid until the thread's next call */
+const char* cmx_repair_text(const uint64_t entry[CMX_REPAIR_WORDS]);
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t*);
 /* Predictor::Pretrain over n dictionary bytes (HOST pointer), before the first submit: only the stages holding
  * `models_` learn (today: contexts + small models); mixers, SSE, LSTM and PPMd are not trained (predictor.cpp:471-487). */

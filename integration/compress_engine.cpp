@@ -61,6 +61,11 @@ void CompressEngine(Predictor* P, const std::vector<uint8_t>& data, cmx_encoder_
   }
   for (size_t c = nchunks > R ? nchunks - R : 0; c < nchunks; ++c) drain(c);
   if (cmx_pipeline_sync(P->pipe())) Predictor::Die();
+  uint64_t rep[2 + CMX_REPAIR_LOG * CMX_REPAIR_WORDS];   // one line per repair on the majority (CMIX_SHADOW_REPAIR): none without an event
+  if (cmx_pipeline_shadow_repairs(P->pipe(), rep, sizeof rep / sizeof rep[0])) Predictor::Die();
+  for (uint64_t i = 0; i < rep[1]; ++i)
+    fprintf(stderr, "\ncmix_amd: repair %llu of %llu: %s", (unsigned long long)(rep[0] - rep[1] + i + 1), (unsigned long long)rep[0], cmx_repair_text(rep + 2 + i * CMX_REPAIR_WORDS));
+  if (rep[1]) fprintf(stderr, "\n");
   for (size_t i = 0; i < R; ++i) { cmx_device_free(dev, d_layer0[i]); cmx_device_free(dev, d_p[i]); }
   cmx_host_free(p);
 }
@@ -129,6 +134,12 @@ int main(int argc, char* argv[]) {
     // CMIX_SHADOW=1|2: that many shadow mixing networks vote on every chunk's probabilities; a disagreement stops the program
     const char* sha = getenv("CMIX_SHADOW");
     if (sha && (sha[0] == '1' || sha[0] == '2') && cmx_pipeline_set_shadow(p.pipe(), sha[0] - '0')) Predictor::Die();
+    // CMIX_SHADOW_REPAIR=N (with CMIX_SHADOW=2 only): up to N times an outvoted instance is repaired from the majority and the compression carries on
+    const char* rep = getenv("CMIX_SHADOW_REPAIR");
+    if (rep && atoi(rep) > 0) {
+      if (!sha || sha[0] != '2') { fprintf(stderr, "cmix_amd: CMIX_SHADOW_REPAIR needs CMIX_SHADOW=2 (a vote of two has no majority)\n"); return 1; }
+      if (cmx_pipeline_set_shadow_repair(p.pipe(), atoi(rep))) Predictor::Die();
+    }
   }
   const double t_ready = since();
   if (enable_preprocess) preprocessor::Pretrain(&p, dictionary);

@@ -53,8 +53,20 @@ class Predictor {
     // CMIX_SHADOW=1|2: that many shadow mixing networks run beside the stream's own and vote on every chunk's probabilities (a decoder is not covered)
     const char* sha = getenv("CMIX_SHADOW");
     if (sha && (sha[0] == '1' || sha[0] == '2') && cmx_set_shadow(h_, sha[0] - '0')) Die();
+    // CMIX_SHADOW_REPAIR=N (with CMIX_SHADOW=2 only): up to N times an outvoted instance is repaired from the majority and the stream carries on
+    const char* rep = getenv("CMIX_SHADOW_REPAIR");
+    if (rep && atoi(rep) > 0) {
+      if (!sha || sha[0] != '2') { fprintf(stderr, "cmix_amd: CMIX_SHADOW_REPAIR needs CMIX_SHADOW=2 (a vote of two has no majority)\n"); exit(1); }
+      if (cmx_set_shadow_repair(h_, atoi(rep))) Die();
+    }
   }
-  ~Predictor() { cmx_destroy(h_); }
+  ~Predictor() {
+    uint64_t rep[2 + CMX_REPAIR_LOG * CMX_REPAIR_WORDS];   // one line per repair on the majority: none without an event
+    if (cmx_shadow_repairs(h_, rep, sizeof rep / sizeof rep[0]) == 0)
+      for (uint64_t i = 0; i < rep[1]; ++i)
+        fprintf(stderr, "cmix_amd: repair %llu of %llu: %s\n", (unsigned long long)(rep[0] - rep[1] + i + 1), (unsigned long long)rep[0], cmx_repair_text(rep + 2 + i * CMX_REPAIR_WORDS));
+    cmx_destroy(h_);
+  }
   Predictor(const Predictor&) = delete;
   Predictor& operator=(const Predictor&) = delete;
 
