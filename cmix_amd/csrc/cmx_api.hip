@@ -497,6 +497,67 @@ int cmx_overlap_probe(const hipStream_t* st, int n, int* distinct) {
 }
 int cmx_cumask_on(void) { return cumask_wanted() && g_cumask_applied; }   // the mixing network's stream really carries its one-XCD mask
 
+// The LDS fill probe (tests/test_gpu_lds_poison.py; no product path calls it): every workgroup writes `pattern` over ALL of its dynamic LDS
+// with ordinary LDS stores, then counts itself in and waits -- bounded by the wall clock, as the overlap probe above -- until all n have
+// arrived. A workgroup holds more than half of a compute unit's LDS (or the grid holds floor(per-CU / per-workgroup) of them per compute
+// unit), so n workgroups resident at once sit on every compute unit and between them have written every LDS they can reach. One word is
+// read back into a global sink so that the stores stay. Vector memory operations only.
+__global__ __launch_bounds__(256) void cmx_lds_fill_kernel(unsigned* cnt, unsigned* seen, unsigned* sink, uint32_t pattern, unsigned words, unsigned n,
+                                                           unsigned long long ticks) {
+  extern __shared__ uint32_t lds_fill[];
+  for (unsigned i = threadIdx.x; i < words; i += 256) lds_fill[i] = pattern;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long t0 = wall_clock64();
+    unsigned c = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (c < n && wall_clock64() - t0 < ticks) { __builtin_amdgcn_s_sleep(8); c = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __hip_atomic_store(seen + blockIdx.x, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();   // the workgroup (and its LDS allocation) stays until its first lane has stopped waiting
+  sink[(size_t)blockIdx.x * 256 + threadIdx.x] = lds_fill[(threadIdx.x * 997u + blockIdx.x) % words];
+}
+int cmx_probe_lds_fill(int device, uint32_t pattern, uint32_t out[8]) {
+  const int fail_value = -1;
+  if (!out) { set_err("cmx_probe_lds_fill: null argument"); return -1; }
+  memset(out, 0, 8 * sizeof(uint32_t));
+  if (cmx_device_count() <= 0) { set_err("cmx_probe_lds_fill: no HIP device"); return -1; }
+  HIP_OK(hipSetDevice(device));
+  HIP_OK(hipDeviceSynchronize());   // no kernel of this process is resident when the fill starts
+  int cus = 0, per_wg = 0, per_cu = 0, khz = 0;
+  HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  HIP_OK(hipDeviceGetAttribute(&per_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+  HIP_OK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device));
+  if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess || per_cu < per_wg) { (void)hipGetLastError(); per_cu = per_wg; }
+  per_wg &= ~3;
+  if (cus <= 0 || cus > 32 * 32 || per_wg < 1024 || khz <= 0) { set_err("cmx_probe_lds_fill: implausible device attributes"); return -1; }
+  const int per = per_cu / per_wg;                // workgroups that fit one compute unit's LDS (1 when a workgroup may hold more than half of it)
+  const unsigned n = (unsigned)(per * cus), words = (unsigned)per_wg / 4;
+  HIP_OK(hipFuncSetAttribute((const void*)cmx_lds_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, per_wg));
+  unsigned* d = nullptr;   // [0] the arrival counter, [1, 1 + n) what each workgroup saw, then the sink (256 words per workgroup)
+  const size_t d_words = 1 + (size_t)n + (size_t)n * 256;
+  HIP_OK(hipMalloc((void**)&d, d_words * 4));
+  const unsigned long long ticks = 50ull * (unsigned long long)khz;   // 50 ms of the wall clock
+  std::vector<unsigned> seen(n);
+  unsigned best = 0, launches = 0;
+  bool ok = true;
+  while (ok && launches < 8 && (launches == 0 || best < n)) {
+    ok = hipMemset(d, 0, (1 + (size_t)n) * 4) == hipSuccess;   // fresh counters for every launch
+    if (!ok) break;
+    hipLaunchKernelGGL(cmx_lds_fill_kernel, dim3(n), dim3(256), (size_t)per_wg, 0, d, d + 1, d + 1 + n, pattern, words, n, ticks);
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(seen.data(), d + 1, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    ++launches;
+    unsigned all = 0;
+    for (unsigned c : seen) all += c >= n;
+    if (all > best) best = all;
+  }
+  (void)hipFree(d);
+  if (!ok) { (void)hipGetLastError(); set_err("cmx_probe_lds_fill: device error"); return -1; }
+  out[0] = best; out[1] = n; out[2] = (uint32_t)per_wg; out[3] = launches;
+  out[4] = (uint32_t)cus; out[5] = (uint32_t)per_cu; out[6] = (uint32_t)(per_cu - per * per_wg);
+  return 0;
+}
+
 // The stream the handle's host-to-device copies go on (the pipeline gives all its stages ONE upload stream that never has
 // a kernel in front of a copy); without it the handle creates its own on first use.
 // Tolerance mode (NOT bit-exact; north_star's "per-bit probabilities within a tolerance"): the layer-0 dot products as f64 tree sums

@@ -150,6 +150,7 @@ def lib():
         L.cmx_pipeline_paq8_role_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_pipeline_last_stage_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_probe_libm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_probe_lds_fill.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
         L.cmx_pipeline_set_tolerance.argtypes = [C.c_void_p, C.c_int]
         L.cmx_pipeline_mixnet_mode.argtypes = [C.c_void_p]
         L.cmx_pipeline_stage_overlap.argtypes = [C.c_void_p]
@@ -355,6 +356,20 @@ def probe_libm(which, x, device=0):
     if lib().cmx_probe_libm(device, which, x.ctypes.data, y.ctypes.data, x.size):
         raise CmxError(last_error())
     return y
+
+
+def lds_fill(pattern, device=0):
+    """Test probe: write the 32-bit `pattern` over the LDS of every compute unit (device synchronise, fill on the null stream, synchronise).
+    -> dict(resident, workgroups, bytes_per_workgroup, launches, compute_units, bytes_per_cu, uncovered_bytes_per_cu, full); `full` means
+    every workgroup saw all others resident at once and no byte of a compute unit's LDS was out of the grid's reach.
+    Never between late_start and late_stop: the decoder's kernels are resident there and the synchronise would wait for them."""
+    out = (C.c_uint32 * 8)()
+    if lib().cmx_probe_lds_fill(device, int(pattern) & 0xFFFFFFFF, out):
+        raise CmxError(last_error())
+    keys = ("resident", "workgroups", "bytes_per_workgroup", "launches", "compute_units", "bytes_per_cu", "uncovered_bytes_per_cu")
+    d = {k: int(out[i]) for i, k in enumerate(keys)}
+    d["full"] = d["workgroups"] > 0 and d["resident"] == d["workgroups"] and d["uncovered_bytes_per_cu"] == 0
+    return d
 
 
 class MixNet:

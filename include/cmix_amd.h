@@ -595,6 +595,24 @@ int cmx_pipeline_stage_totals(cmx_pipeline_t*, double ms[3], uint64_t* chunks, i
  * ------------------------------------------------------------------------ */
 int cmx_probe_libm(int device, int which, const float* x, float* y, size_t n);
 
+/* ------------------------------------------------------------------------
+ * LDS fill probe (tests only, no product path calls it): writes `pattern` over the LDS of every compute
+ * unit of the device, so that the next kernel launched finds that pattern, not what its own previous launch left, in every
+ * LDS word it has not written itself. Synchronises the device first, runs on the null stream and synchronises again:
+ * the fill runs while no kernel of this process is resident and is complete when the call returns.
+ * One workgroup of 256 threads per compute unit (floor(per-CU LDS / per-workgroup maximum) of them where a workgroup may hold
+ * at most half a compute unit's LDS), each with the device's largest per-workgroup LDS; a launch counts as complete when every
+ * workgroup saw all the others resident at once (two do not fit one compute unit, so they sit on all of them). Up to 8
+ * launches per call, the best one is reported.
+ * out: [0] workgroups that saw all others resident, [1] workgroups launched, [2] LDS bytes written per workgroup,
+ *      [3] launches used, [4] compute units, [5] LDS bytes per compute unit, [6] bytes per compute unit the grid cannot reach
+ *      (0 on the MI355X), [7] 0. Full coverage: out[0] == out[1] and out[6] == 0.
+ * Returns 0, or -1 on a HIP error (cmx_last_error).
+ * NEVER call it between cmx_pipeline_late_start and _late_stop (or any stage's late start / stop): the decoder's kernels
+ * stay resident waiting for the host, and the device synchronise here would wait for them until their 30 s timeout.
+ * ------------------------------------------------------------------------ */
+int cmx_probe_lds_fill(int device, uint32_t pattern, uint32_t out[8]);
+
 /* ---- 2f. The paq8 stage: layer-0 columns 434..2024 = the 1591 values PAQ8::Predict() returns per bit (replaces
  *        src/models/paq8.{h,cpp} as wired at src/predictor.cpp:85-97: PAQ8::Predict / Perceive around
  *        paq8::Predictor::update, reference src/models/paq8.cpp:8248-8362, and contextModel2 :8101-8207).

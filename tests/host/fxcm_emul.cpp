@@ -3,6 +3,18 @@
 // workgroup replaced by a loop over thread ids per phase -- in a seeded shuffled order, so that a phase in which one
 // thread reads what another writes shows up as a mismatch against the oracle (tests/test_fxcm_stage_host.py).
 // Not a fallback: nothing in cmix_amd/ loads this library.
+//
+// LDS audit (fxe_set_poison): what fx_roles_body (cmix_amd/csrc/fxcm_stage.hip) keeps in LDS, and what stands for it here. With a poison
+// byte set, every emulated object is filled with it at the start of each fxe_run -- the point of a kernel launch, before fxd_load_shared --
+// so a word the body reads before the launch wrote it shows as a mismatch against the oracle. FxDev and everything zalloc hands out stand
+// for device global memory (hipMemset zeroes it) and are left alone.
+//   __shared__ object of the kernel                              here
+//   FxShared (fx_smem, dynamic)                                  Emul::sh: emulated, poisoned
+//   FxLocal (fx_smem, behind it): the working copy of FxDev,     device-only: the host body reads FxDev and the tables in place
+//     squash / stretch / wrt / sta, rec[2], apm rows, ex[2]        (tests/test_gpu_lds_poison.py)
+//   FxAhead ah (bytes and LSTM hints staged a byte ahead)        device-only: fxd_bit reads the chunk's arrays
+//   res8_s, scr_s, mscx, merr, apmcx, apmspec, msw               device-only: role X's wave-parallel forms of phases 2 / 3 / 5
+//   pbp (profile clocks), late_go (decoder's form)               device-only
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -19,7 +31,7 @@ struct HostPolicy {
   void pattern16(void* p, size_t n, const uint16_t* pat, int plen) { uint16_t* q = (uint16_t*)p; for (size_t i = 0; i < n; i++) q[i] = pat[i % (size_t)plen]; }
   void upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); }
 };
-struct Emul { FxDev dev; FxShared sh; HostPolicy pol; FxParser* parser; uint32_t rng; int order[FX_THREADS]; uint64_t bits_maps = 0, bits_serial = 0; uint64_t serial_by[FX_NMAPS][8] = {}; };
+struct Emul { FxDev dev; FxShared sh; HostPolicy pol; FxParser* parser; uint32_t rng; int order[FX_THREADS]; uint64_t bits_maps = 0, bits_serial = 0; uint64_t serial_by[FX_NMAPS][8] = {}; int poison = -1; };
 void shuffle(Emul* e) {
   for (int i = FX_THREADS - 1; i > 0; i--) {
     e->rng = e->rng * 1664525u + 1013904223u;
@@ -53,6 +65,7 @@ int fxe_run(void* h, const uint8_t* bytes, int n, const int16_t* lstmpr, const u
   std::vector<FxByteRec> recs((size_t)n);
   if (fxp_run(e->parser, bytes, n, recs.data()) != 0) return -1;
   const int nbits = 8 * n, blpos0 = d->blpos, lastbyte0 = d->lastbyte, have0 = d->have_rec;
+  if (e->poison >= 0) memset(sh, e->poison, sizeof *sh);   // what the LDS held before the launch is not the stream's
   for (int t = 0; t < FX_THREADS; t++) fxd_load_shared(d, sh, t);
   for (int i = 0; i < FX_OUTPUTS; i++) out[i] = d->pending[i];
   for (int q = 0; q < nbits; q++) {
@@ -71,6 +84,8 @@ int fxe_run(void* h, const uint8_t* bytes, int n, const int16_t* lstmpr, const u
   return 0;
 }
 void fxe_set_serial_maps(void* h, int serial) { ((Emul*)h)->dev.slot_parallel = !serial; }
+// every later fxe_run starts with all that models LDS filled with this byte (see the audit at the top); < 0: off (the LDS keeps what the last run left)
+void fxe_set_poison(void* h, int byte) { ((Emul*)h)->poison = byte < 0 ? -1 : (byte & 0xff); }
 // how often a map fell back to its serial walk: [0] map-bits in total, [1] serial ones
 void fxe_conflict_stats(void* h, uint64_t* out2) { out2[0] = ((Emul*)h)->bits_maps; out2[1] = ((Emul*)h)->bits_serial; }
 // ... by map and bit position: out[31][8]

@@ -14,7 +14,7 @@ struct HostPolicy {
   void* zalloc(size_t bytes) { void* p = calloc(bytes + 64, 1); blocks.push_back(p); return p; }
   void upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); }
 };
-struct Emul { P8Cm2Dev dev; P8Cm2Shared sh; HostPolicy pol; uint32_t rng; int order[P8CM2_MAXC]; uint64_t steps = 0, serial = 0; };
+struct Emul { P8Cm2Dev dev; P8Cm2Shared sh; HostPolicy pol; uint32_t rng; int order[P8CM2_MAXC]; uint64_t steps = 0, serial = 0; int poison = -1; };
 }  // namespace
 
 extern "C" {
@@ -30,11 +30,13 @@ void p8e_destroy(void* h) { Emul* e = (Emul*)h; for (void* p : e->pol.blocks) fr
 void p8e_hash(uint64_t ctx, uint32_t index, uint64_t size_bytes, uint32_t* ctx32, uint16_t* chk16) { p8b::hash(ctx, index, p8b::hashbits(size_bytes), ctx32, chk16); }
 // start in the middle of a stream: the partial-byte register and the last coded bit as ContextMap2 would hold them
 void p8e_seed(void* h, uint32_t bits, int last_y) { ((Emul*)h)->dev.bits = bits; ((Emul*)h)->dev.last_y = last_y; }
+void p8e_set_poison(void* h, int byte) { ((Emul*)h)->poison = byte < 0 ? -1 : (byte & 0xff); }   // every later p8e_run starts from LDS filled with this byte; < 0: off
 void p8e_stats(void* h, uint64_t* out2) { out2[0] = ((Emul*)h)->steps; out2[1] = ((Emul*)h)->serial; }
 int p8e_run(void* h, const uint32_t* ctx, const uint16_t* chk, const uint8_t* bits, int nbytes, int16_t* out) {
   Emul* e = (Emul*)h;
   P8Cm2Dev* d = &e->dev;
   P8Cm2Shared* sh = &e->sh;
+  if (e->poison >= 0) memset(sh, e->poison, sizeof *sh);   // the first design's shared body: nothing of the last launch's survives
   sh->r = d->regs;
   uint32_t run_bits = d->bits;
   int last_y = d->last_y;

@@ -14,7 +14,7 @@ struct HostPolicy {
   void* zalloc(size_t bytes) { void* p = calloc(bytes + 64, 1); blocks.push_back(p); return p; }
   void upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); }
 };
-struct Emul { P8CmDev dev; P8CmShared sh; HostPolicy pol; uint32_t rng; int order[P8CM_MAXS]; uint64_t steps = 0, serial = 0, draws = 0; };
+struct Emul { P8CmDev dev; P8CmShared sh; HostPolicy pol; uint32_t rng; int order[P8CM_MAXS]; uint64_t steps = 0, serial = 0, draws = 0; int poison = -1; };
 }  // namespace
 
 extern "C" {
@@ -27,11 +27,16 @@ void* p8f_create(int ninst, const uint64_t* sizes, const int* counts, const uint
   return e;
 }
 void p8f_destroy(void* h) { Emul* e = (Emul*)h; for (void* p : e->pol.blocks) free(p); delete e; }
+void p8f_set_poison(void* h, int byte) { ((Emul*)h)->poison = byte < 0 ? -1 : (byte & 0xff); }   // every later p8f_run starts from LDS filled with this byte; < 0: off
 void p8f_stats(void* h, uint64_t* out3) { Emul* e = (Emul*)h; out3[0] = e->steps; out3[1] = e->serial; out3[2] = e->draws; }
 int p8f_run(void* h, const uint32_t* ctx, const uint16_t* chk, const uint8_t* bits, int nbytes, int16_t* out) {
   Emul* e = (Emul*)h;
   P8CmDev* d = &e->dev;
   P8CmShared* sh = &e->sh;
+  if (e->poison >= 0) {   // P8CmShared is cmx_p8s_xfam_kernel's LDS: nothing of the last launch's survives; the kernel's first lane sets the active range every byte
+    memset(sh, e->poison, sizeof *sh);
+    sh->act_lo = sh->act_hi = 0;   // (a stand-alone family calls every context: no body here stores the range, so these two words cannot show a read before a write)
+  }
   sh->r = d->regs; sh->rnd = d->rnd;
   int last_y = d->last_y, c1 = d->c1;
   const int S = d->nslots;

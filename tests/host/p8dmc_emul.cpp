@@ -14,7 +14,7 @@ struct HostPolicy {
   void* zalloc(size_t bytes) { void* p = calloc(bytes + 64, 1); blocks.push_back(p); return p; }
   void upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); }
 };
-struct Emul { P8DmcDev dev; P8DmcShared sh; HostPolicy pol; uint64_t resets = 0; };
+struct Emul { P8DmcDev dev; P8DmcShared sh; HostPolicy pol; uint64_t resets = 0; int poison = -1; };
 }  // namespace
 
 extern "C" {
@@ -22,9 +22,11 @@ void* p8x_create(int level, const uint8_t* nex, const int16_t* stretch) { Emul* 
 void p8x_destroy(void* h) { Emul* e = (Emul*)h; for (void* p : e->pol.blocks) free(p); delete e; }
 // start mid-stream: the last coded bit and the number of bits coded so far
 void p8x_seed(void* h, int last_y, uint32_t bits_done) { ((Emul*)h)->dev.last_y = last_y; ((Emul*)h)->dev.bits_done = bits_done; }
+void p8x_set_poison(void* h, int byte) { ((Emul*)h)->poison = byte < 0 ? -1 : (byte & 0xff); }   // every later p8x_run starts from LDS filled with this byte; < 0: off
 uint64_t p8x_resets(void* h) { return ((Emul*)h)->resets; }
 void p8x_run(void* h, const uint8_t* bits, int nbits, int16_t* out) {
   Emul* e = (Emul*)h;
+  if (e->poison >= 0) memset(&e->sh, e->poison, sizeof e->sh);   // P8DmcShared is the kernel's LDS: nothing of the last launch's survives
   int y = e->dev.last_y;
   const uint32_t done = e->dev.bits_done;
   for (int t = 0; t < nbits; t++) {

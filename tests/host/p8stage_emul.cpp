@@ -4,6 +4,29 @@
 // by the same p8stage_build.h with a calloc policy. Only the mixer's dot products / training are plain loops here (on
 // the device they are wave-parallel code, p8stage.hip). tests/test_p8stage_host.py compares its 1591 values per step
 // with columns 434..2024 of traces of the unmodified reference. Nothing in cmix_amd/ loads it.
+//
+// LDS audit (p8s_set_poison): the __shared__ objects of the kernels of cmix_amd/csrc/p8stage.hip, and what stands for them here. With a
+// poison byte set, every emulated object is filled with it at the start of each p8s_run -- the point of the kernels' launch, before
+// p8c2_load / p8f_load -- so a word a body reads before the launch wrote it shows as a mismatch against the reference's trace. P8StageState
+// and everything zalloc hands out stand for device global memory (hipMemset zeroes it) and are left alone, and so is what has no LDS
+// counterpart at all: the registers of the first-design bodies (`r`: on the device a launch loads them from P8CmDev::regs / P8Cm2Dev::regs
+// before its first step; here the copy in the shared struct IS their home between runs) and an image model's copy of the generator (`rnd`).
+//   kernel                         __shared__ object                                      here
+//   cmx_p8s_cm2v2_kernel (+ late)  P8Cm2V2Shared sh                                       Emul::c2[k]: emulated, poisoned whole
+//     late form only               late_y_s, ctx_s, chk_s                                 device-only (tests/test_gpu_lds_poison.py)
+//   cmx_p8s_fam2_kernel (+ late)   P8FamShared + StateMaps (p8f_smem, dynamic)            Emul::f2mem: emulated, poisoned whole
+//     late form only               late_y_s, fctx_s, fchk_s                               device-only
+//   cmx_p8s_dmc_kernel (+ late)    P8DmcShared sh (late: + late_y_s)                      Emul::dsh: emulated, poisoned whole
+//   cmx_p8s_xfam_kernel            P8CmShared sh                                          Emul::xsh[m]: emulated, poisoned but r of the model's
+//                                                                                           slots and rnd (the launch loads exactly those)
+//   (no kernel: CMX_P8FAM_V1)      first-design P8CmShared / P8Cm2Shared                  Emul::fsh, csh[k]: poisoned but r (fsh: and rnd, and act_lo /
+//                                                                                           act_hi, which only cmx_p8s_xfam_kernel's first lane stores:
+//                                                                                           reset to 0 for these bodies, so they cannot show as read
+//                                                                                           before written here; xsh[m] keeps them poisoned)
+//   mixer main + helpers, plain    xs, outs, pr_s, res_s, st_s, arow, p_s, fin_s,         device-only: the mixer here is plain loops over the
+//     and late, and cmx_p8s_xmix     squash, stretch, ring_sel / ring_apm / ring_ord /      stage's arrays
+//                                    ring_bit, sel_s, apm_s, ord_s, late_y_s
+//   lanes / xlanes kernels         (registers only; late form: late_y_s)                  --
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -47,10 +70,34 @@ struct Emul {
                           // handed in, and the maps' uniform registers take that bit at the top of the step (p8d_bit_y, p8f_uni_tail + p8f_uni_head)
   int fam_miniwalk = 1;   // 0: whole-instance walks only; 1: the kernel's narrowed walk; 2: with every second visit treated as unlisted (the fall-back path)
   uint64_t fam_mini = 0, fam_mini_full = 0;
+  int poison = -1;        // >= 0: every run starts with all that models LDS filled with this byte (the audit at the top)
   // diagnostics: per family instance, lookup bits with an overlap / with an overlap AND a pending rnd() draw in the instance
   uint64_t inst_conf[P8CM_MAXI] = {}, inst_risky[P8CM_MAXI] = {}, lookups = 0, bits_with_conf = 0, bits_with_risky = 0, draws_total = 0, multi_conf = 0;
 };
 int16_t sat16(int v) { return (int16_t)(v > 32767 ? 32767 : v < -32768 ? -32768 : v); }
+// A first-design body as a launch finds it: everything poisoned but the registers of its nslots contexts and the generator, which the launch loads from global memory
+void poison_cm(P8CmShared* sh, int nslots, int b) {
+  const P8CmRegs r = sh->r;
+  const P8Rnd rnd = sh->rnd;
+  memset(sh, b, sizeof *sh);
+  for (int s = 0; s < nslots; s++) { sh->r.cp[s] = r.cp[s]; sh->r.cp0[s] = r.cp0[s]; sh->r.runp[s] = r.runp[s]; sh->r.sm_cxt[s] = r.sm_cxt[s]; }
+  sh->rnd = rnd;
+}
+void poison_shared(Emul* e) {
+  const int b = e->poison;
+  if (b < 0) return;
+  for (int k = 0; k < P8_NCM2; k++) {
+    memset(e->c2[k], b, sizeof *e->c2[k]);
+    const P8Cm2Regs r = e->csh[k].r;
+    memset(&e->csh[k], b, sizeof e->csh[k]);
+    e->csh[k].r = r;
+  }
+  memset(e->f2mem.data(), b, e->f2mem.size());
+  memset(&e->dsh, b, sizeof e->dsh);
+  poison_cm(&e->fsh, e->S.fam.nslots, b);
+  e->fsh.act_lo = e->fsh.act_hi = 0;   // (the generic family calls every context; cmx_p8s_xfam_kernel's first lane stores a model's range every byte)
+  for (int m = 0; m < P8_NMODEL - 1; m++) poison_cm(&e->xsh[m], e->S.xfam[m].nslots, b);
+}
 int dot(const int16_t* t, const int16_t* w, int n) {
   uint32_t sum = 0;
   for (int i = 0; i + 1 < n; i += 2) {
@@ -126,6 +173,7 @@ void p8s_layout_dump(void* h) {
   for (int m = 0; m < P8_NMODEL - 1; m++) printf("image model %d: prefix %d nx %d lanes %d contexts %d (first at %d)\n", m + 1, L.xl[m].prefix_nx, L.xl[m].nx, L.xl[m].nlanes, L.xl[m].fam_count, L.xl[m].fam_off[0]);
 }
 void p8s_set_miniwalk(void* h, int mode) { ((Emul*)h)->fam_miniwalk = mode; }
+void p8s_set_poison(void* h, int byte) { ((Emul*)h)->poison = byte < 0 ? -1 : (byte & 0xff); }   // < 0: off (the LDS keeps what the last run left)
 void p8s_set_late(void* h, int on) { ((Emul*)h)->late = on & 1; ((Emul*)h)->late_models = (on >> 1) & 1; }
 void p8s_miniwalk_stats(void* h, uint64_t* out2) { out2[0] = ((Emul*)h)->fam_mini; out2[1] = ((Emul*)h)->fam_mini_full; }
 uint32_t p8s_rnd_i(void* h) { return ((Emul*)h)->f2_i; }   // how many values of the shared generator the family has drawn (mod 2^32)
@@ -167,6 +215,7 @@ int p8s_run(void* h, const uint8_t* bytes, int nbytes, float* out) {
   P8FamRun f_run; f_run.last_y = S.fam.last_y; f_run.c1 = S.fam.c1; f_run.lk = 0; f_run.c0 = 1; f_run.bits8 = 0; f_run.order = 0; f_run.nslots = S.fam.nslots; f_run.row_stride = S.fam.row_stride;   // as cmx_p8s_fam2_kernel starts a chunk
   uint32_t run_bits[P8_NCM2]; int c_last_y[P8_NCM2];
   for (int k = 0; k < P8_NCM2; k++) { run_bits[k] = S.cm2[k].bits; c_last_y[k] = S.cm2[k].last_y; }
+  poison_shared(e);   // (the generator is the generic family's between runs: fam_owner == 0 here)
   if (!e->use_v1)
     for (int k = 0; k < P8_NCM2; k++) {
       for (int tid = 0; tid < P8CM2_MAXC; tid++) p8c2_load(&S.cm2[k], e->c2[k], tid, P8CM2_MAXC);

@@ -56,8 +56,11 @@ def oracle_rows(data, lstmpr, lstmex, dictionary=None, blpos=0):
     return rows
 
 
-def run_emul(L, data, lstmpr, lstmex, chunks, seed=12345, dictionary=None, blpos=0, serial_maps=False, stats=None):
+def run_emul(L, data, lstmpr, lstmex, chunks, seed=12345, dictionary=None, blpos=0, serial_maps=False, stats=None, poison=None):
     h = L.fxe_create(dictionary, seed)
+    if poison is not None:   # FxShared is refilled with this byte at the start of every fxe_run (tests/host/fxcm_emul.cpp, the audit at its top)
+        L.fxe_set_poison.argtypes = [C.c_void_p, C.c_int]
+        L.fxe_set_poison(h, poison)
     if serial_maps:
         L.fxe_set_serial_maps.argtypes = [C.c_void_p, C.c_int]
         L.fxe_set_serial_maps(h, 1)
@@ -107,6 +110,37 @@ def test_text_vs_oracle_ragged_chunks():
     # the slot-parallel path is the one exercised, and its serial fallback (two contexts of a map in one bucket) occurs
     assert 0 < stats[1] < stats[0] // 4, stats
     compare(run_emul(L, data[:2500], pr, ex, [2500], serial_maps=True), want, "one lane per map")
+
+
+POISON = [0xFF, 0xA5, 0x00]   # what the LDS model holds when a run ("launch") begins: all bits set, a non-trivial byte, a fresh device's zeros
+_poison_ref = {}
+
+
+def _poison_case():
+    """enwik-like text, LSTM hints and the oracle's rows: computed once for all poison bytes"""
+    if not _poison_ref:
+        from cmix_amd import synth
+        data = np.frombuffer(synth.enwik_like(2500, 31), np.uint8)
+        pr, ex = hints(8 * len(data), 7)
+        _poison_ref["case"] = (data, pr, ex, oracle_rows(data, pr, ex))
+    return _poison_ref["case"]
+
+
+@pytest.mark.parametrize("poison", POISON)
+def test_poisoned_lds_ragged_chunks_vs_oracle(poison):
+    """Nothing the body reads from FxShared may be what the previous launch left there: with the whole struct refilled with a byte at the
+    start of every run (on the device another kernel may have had the compute unit in between), ragged chunks still give the oracle's rows."""
+    data, pr, ex, want = _poison_case()
+    stats = []
+    got = run_emul(emul(), data, pr, ex, [1, 1, 7, 100, 1000, 3, 2000], stats=stats, poison=poison)
+    compare(got, want, "poison 0x%02X" % poison)
+    assert 0 < stats[1] < stats[0], stats   # both the slot-parallel path and its serial fallback ran
+
+
+@pytest.mark.parametrize("poison", POISON)
+def test_poisoned_lds_one_lane_per_map_vs_oracle(poison):
+    data, pr, ex, want = _poison_case()
+    compare(run_emul(emul(), data[:1200], pr, ex, [1, 7, 500, 1000], serial_maps=True, poison=poison), want, "one lane per map, poison 0x%02X" % poison)
 
 
 @pytest.mark.parametrize("flavour", ["binary", "runs", "markup"])

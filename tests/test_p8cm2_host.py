@@ -93,10 +93,13 @@ def hashed(L, cx, size_bytes):
     return c32, k16
 
 
-def run_emul(L, size_bytes, count, data, cx, chunks, seed=777, serial=0, stats=None):
+def run_emul(L, size_bytes, count, data, cx, chunks, seed=777, serial=0, stats=None, poison=None):
     nex, stretch, ilog = tables()
     h = L.p8e_create(size_bytes, count, nex.ctypes.data, stretch.ctypes.data, ilog.ctypes.data, seed, serial)
     assert h
+    if poison is not None:   # P8Cm2Shared is refilled with this byte at the start of every p8e_run
+        L.p8e_set_poison.argtypes = [C.c_void_p, C.c_int]
+        L.p8e_set_poison(h, poison)
     c32, k16 = hashed(L, cx, size_bytes)
     bits = np.unpackbits(np.ascontiguousarray(data, np.uint8))
     out = np.zeros((8 * len(data), 7 * count), np.int16)
@@ -137,6 +140,28 @@ def test_vs_oracle(size_bytes, count, nbytes, flavour):
         assert stats[1] < stats[0] // 2, stats       # and the lane-per-context path is the common one otherwise
     got = run_emul(L, size_bytes, count, data[:600], cx[:600], [600], serial=1)
     assert np.array_equal(got, want[:8 * 600])
+
+
+POISON = [0xFF, 0xA5, 0x00]   # what the LDS model holds when a run ("launch") begins: all bits set, a non-trivial byte, a fresh device's zeros
+_poison_ref = {}
+
+
+@pytest.mark.parametrize("poison", POISON)
+def test_poisoned_lds_vs_oracle(poison):
+    """Nothing the body reads from P8Cm2Shared may be what the previous launch left there: refilled with a byte at the start of every run,
+    ragged chunks still give the oracle's rows (the colliding contexts: lane-per-context steps and serial walks both occur)."""
+    size_bytes, count, nbytes = 1 << 16, 20, 1500
+    if not _poison_ref:
+        from cmix_amd import synth
+        data = np.frombuffer(synth.enwik_like(nbytes, 13), np.uint8)
+        cx = contexts(data, count, "collide")
+        _poison_ref["case"] = (data, cx, oracle_rows(size_bytes, count, data, cx))
+    data, cx, want = _poison_ref["case"]
+    stats = []
+    got = run_emul(emul(), size_bytes, count, data, cx, [1, 7, 500, 1000], stats=stats, poison=poison)
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, ("poison 0x%02X" % poison, "first mismatch (step, input):", bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
+    assert 0 < stats[1] < stats[0], stats
 
 
 def test_order_n_map_vs_golden_columns():

@@ -102,11 +102,14 @@ def hashed(sizes, counts, cxs):
     return c32, k16
 
 
-def run_emul(L, sizes, counts, data, cxs, chunks, seed=4242, serial=0, stats=None):
+def run_emul(L, sizes, counts, data, cxs, chunks, seed=4242, serial=0, stats=None, poison=None):
     nex, stretch, ilog = tables()
     sz, ct = np.array(sizes, np.uint64), np.array(counts, np.int32)
     h = L.p8f_create(len(sizes), sz.ctypes.data, ct.ctypes.data, nex.ctypes.data, stretch.ctypes.data, ilog.ctypes.data, seed, serial)
     assert h
+    if poison is not None:   # P8CmShared is refilled with this byte at the start of every p8f_run
+        L.p8f_set_poison.argtypes = [C.c_void_p, C.c_int]
+        L.p8f_set_poison(h, poison)
     c32, k16 = hashed(sizes, counts, cxs)
     bits = np.unpackbits(np.ascontiguousarray(data, np.uint8))
     S = sum(counts)
@@ -151,6 +154,27 @@ def test_family_vs_oracle():
     assert draws > 1000 and 0 < serial < steps, stats    # both paths ran, and the generator was actually consumed in the parallel one
     got = run_emul(L, SIZES, COUNTS, data[:500], [c[:500] for c in cxs], [500], serial=1)
     assert np.array_equal(got, want[:8 * 500])
+
+
+POISON = [0xFF, 0xA5, 0x00]   # what the LDS model holds when a run ("launch") begins: all bits set, a non-trivial byte, a fresh device's zeros
+_poison_ref = {}
+
+
+@pytest.mark.parametrize("poison", POISON)
+def test_poisoned_lds_family_vs_oracle(poison):
+    """Nothing the body reads from P8CmShared may be what the previous launch left there: refilled with a byte at the start of every run,
+    ragged chunks still give the oracle's rows, on the lane-per-context path and on the serial walk."""
+    if not _poison_ref:
+        data = stream(1600)
+        cxs = family_contexts(data, COUNTS, 3)
+        _poison_ref["case"] = (data, cxs, oracle_rows(SIZES, COUNTS, data, cxs)[0])
+    data, cxs, want = _poison_ref["case"]
+    stats = []
+    got = run_emul(emul(), SIZES, COUNTS, data, cxs, [1, 9, 700, 5000], stats=stats, poison=poison)
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, ("poison 0x%02X" % poison, "first mismatch (step, input):", bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
+    steps, serial, draws = stats
+    assert draws > 0 and 0 < serial < steps, stats
 
 
 def test_generator_position_after_the_parallel_path():

@@ -78,6 +78,42 @@ def test_vs_oracle(level, nbytes):
     assert (resets > 0) == (level == 0), resets
 
 
+POISON = [0xFF, 0xA5, 0x00]   # what the LDS model holds when a run ("launch") begins: all bits set, a non-trivial byte, a fresh device's zeros
+_poison_ref = {}
+
+
+@pytest.mark.parametrize("poison", POISON)
+def test_poisoned_lds_vs_oracle(poison):
+    """Nothing the body reads from P8DmcShared (the ten stretched predictions, the reset flags) may be what the previous launch left there:
+    refilled with a byte at the start of every run, ragged chunks -- ends inside a byte included -- still give the oracle's rows, resets and all."""
+    level = 0
+    if not _poison_ref:
+        from cmix_amd import synth
+        data = np.frombuffer(synth.enwik_like(40000, 29), np.uint8)
+        _poison_ref["case"] = (data, oracle_rows(level, data))
+    data, want = _poison_ref["case"]
+    L = emul()
+    L.p8x_set_poison.argtypes = [C.c_void_p, C.c_int]
+    nex, stretch, _ = tables()
+    h = L.p8x_create(level, nex.ctypes.data, stretch.ctypes.data)
+    L.p8x_set_poison(h, poison)
+    bits = np.unpackbits(np.ascontiguousarray(data))
+    got = np.zeros((len(bits), 6), np.int16)
+    pos = 0
+    for n in [1, 3, 13, 8000, 150000, 1 << 30]:
+        n = min(n, len(bits) - pos)
+        if n <= 0:
+            break
+        b, o = np.ascontiguousarray(bits[pos:pos + n]), got[pos:pos + n]
+        L.p8x_run(h, b.ctypes.data, n, o.ctypes.data)
+        pos += n
+    resets = L.p8x_resets(h)
+    L.p8x_destroy(h)
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, ("poison 0x%02X" % poison, "first mismatch (bit, input):", bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
+    assert resets > 0, resets
+
+
 def test_vs_golden_columns():
     """cmix sees paq8's mixer inputs as squash(x) / 4095 (paq8.cpp:542-545). The forest's six inputs at cmix's level 11,
     started the way paq8's Predictor starts (first call after one coded bit), must appear as six consecutive layer-0

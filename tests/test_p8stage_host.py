@@ -46,7 +46,7 @@ def emul():
     return L
 
 
-def run_stage(data, chunks=None, miniwalk=None, mini_stats=None, late=False):
+def run_stage(data, chunks=None, miniwalk=None, mini_stats=None, late=False, poison=None):
     """PAQ8::Predict()'s 1591 values before every bit of data, through the emulated stage in the given chunk sizes. miniwalk: how the
     ContextMap family resolves an overlap at a lookup bit (None / 1: as the kernel, 0: whole-instance walks, 2: the fall-back path forced)."""
     L = emul()
@@ -59,6 +59,9 @@ def run_stage(data, chunks=None, miniwalk=None, mini_stats=None, late=False):
     if late:
         L.p8s_set_late.argtypes = [C.c_void_p, C.c_int]
         L.p8s_set_late(h, int(late))   # 1: the decoder's order; 3: for the steps of the models with their own tables too
+    if poison is not None:   # everything that models LDS is refilled with this byte at the start of every p8s_run (tests/host/p8stage_emul.cpp, the audit at its top)
+        L.p8s_set_poison.argtypes = [C.c_void_p, C.c_int]
+        L.p8s_set_poison(h, poison)
     out = np.zeros((8 * len(data), 1591), np.float32)
     pos, k = 0, 0
     chunks = chunks or [len(data)]
@@ -220,6 +223,34 @@ def test_decoders_order_of_operations_on_media_streams(name, nbytes):
     got, _ = run_stage(stream[:nbytes], chunks=[512, 77, 300], late=3)
     bad = np.nonzero(row_hash(got) != want[:8 * nbytes])[0]
     assert bad.size == 0, (name, "first differing step:", bad[0], "of", 8 * nbytes)
+
+
+POISON = [0xFF, 0xA5, 0x00]   # what the LDS model holds when a run ("launch") begins: all bits set, a non-trivial byte, a fresh device's zeros
+
+
+@pytest.mark.parametrize("poison", POISON)
+@pytest.mark.parametrize("late", [False, True])
+def test_poisoned_lds_golden_columns_ragged_chunks(late, poison):
+    """Nothing a body reads from its LDS may be what the previous launch left there: with every shared struct refilled with a byte at the start
+    of each run, ragged chunks still give the reference's columns -- in the compressor's and in the decoder's order of operations."""
+    g = load_golden("text_96")
+    want = np.ascontiguousarray(mg.unpack_probs(g)[:, 434:2025])
+    got, _ = run_stage(g["stream"], chunks=[1, 7, 40, 13] if late else [1, 1, 7, 30], late=late, poison=poison)
+    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+    assert bad.size == 0, ("poison 0x%02X" % poison, "late" if late else "plain", "first mismatch (step, column):", bad[0])
+
+
+@pytest.mark.parametrize("poison", POISON)
+@pytest.mark.parametrize("late", [False, 3])
+def test_poisoned_lds_media_stream(late, poison):
+    """... and across the switches between the generic models and a model with tables of its own (audio: the model's family holds generic
+    ContextMaps whose state changes hands, the first design's shared body runs the model's map), chunk ends inside the model's bytes included."""
+    from make_paq8_hashes import row_hash
+    stream, want = load_hashes("wav8m_2k")
+    nbytes = 1949
+    got, _ = run_stage(stream[:nbytes], chunks=[512, 77, 300], late=late, poison=poison)
+    bad = np.nonzero(row_hash(got) != want[:8 * nbytes])[0]
+    assert bad.size == 0, ("poison 0x%02X" % poison, late, "first differing step:", bad[0], "of", 8 * nbytes)
 
 
 def test_model_step_inside_a_text_block_is_coded():
