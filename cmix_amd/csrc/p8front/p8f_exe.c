@@ -1,10 +1,12 @@
 /* p8front/p8f_exe.c -- HOST FRONT END of the paq8 stage (product code; tables are recorded through p8f_emit.h, the device learns).
+ * One text, two back ends: the oracle's Makefile builds this same file a second time, with the p8f_* calls below mapped onto its CPU learners
+ * (paq8_names.h there), so the class-level tests against the unmodified reference pin the text that ships.
  *
  * Host front end for paq8's exeModel (reference src/models/paq8.cpp:6560-7546): an x86/x64 instruction-boundary decoder
  * (prefixes, REX, 1/2/3-byte opcodes, ModRM/SIB, immediates and displacements; opcode tables in p8f_tables.h,
  * dumped from the reference build) whose parser state, a cache of the last 32 quantised instructions and sparse
  * byte contexts feed a 20-context ContextMap2 and six mixer weight-set selectors. contextModel2 runs it with
- * Forced = true on every input, text included. Parity: tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). */
+ * Forced = true on every input, text included. Pinned against the reference's own function in tests/test_oracle_paq8core.py (the oracle's build of this file) and, as built for the product, by tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>

@@ -1,10 +1,11 @@
 /* p8front/p8f_record.c -- HOST FRONT END of the paq8 stage (product code; tables are recorded through p8f_emit.h, the device learns).
+ * One text, two back ends: the oracle's Makefile builds this same file a second time, with the p8f_* calls below mapped onto its CPU learners
+ * (paq8_names.h there), so the class-level tests against the unmodified reference pin the text that ships.
  *
  * Host front end for paq8's recordModel (reference src/models/paq8.cpp:4204-4433): detection of a fixed record length
  * from byte-recurrence distances (two candidates with counters, dBASE headers), column / row-neighbour contexts into
  * four ContextMaps, six StationaryMaps, three IndirectMaps, three SmallStationaryContextMaps, five IndirectContexts,
- * and three mixer weight-set selectors. It runs on every block type, text included. Pinned against the reference's own
- * function in tests/test_oracle_paq8core.py. */
+ * and three mixer weight-set selectors. It runs on every block type, text included. Pinned against the reference's own function in tests/test_oracle_paq8core.py (the oracle's build of this file) and, as built for the product, by tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>

@@ -1,11 +1,13 @@
 /* p8front/p8f_stem.c -- HOST FRONT END of the paq8 stage (product code; tables are recorded through p8f_emit.h, the device learns).
+ * One text, two back ends: the oracle's Makefile builds this same file a second time, with the p8f_* calls below mapped onto its CPU learners
+ * (paq8_names.h there), so the class-level tests against the unmodified reference pin the text that ships.
  *
  * Host front end for paq8's Word (reference src/models/paq8.cpp:1545-1622) and EnglishStemmer (:1764-2431), a Porter2
  * derivative with prefix / superlative handling and word-class flags, used by wordModel and TextModel. The suffix and
  * exception lists are data extracted from the reference (p8f_stem_tables.h, scripts/gen_paq8_stem_tables.py);
  * the control flow below follows the reference step by step because the stem, the flags and the hashes of every word
- * have to come out identical. Pinned in tests/test_p8front_twins.py (THIS file's objects against the reference's own class on a 6 000-word vocabulary
- * and its inflected forms; tests/test_oracle_paq8core.py pins the oracle's twin, oracle/paq8_stem.c, the same way). */
+ * have to come out identical. Pinned against the reference's own classes on its 44 k-word dictionary and inflected forms (tests/test_oracle_paq8core.py, the oracle's
+ * build of this file) and again through the product library's own objects (tests/test_p8front_twins.py). */
 #include <ctype.h>
 #include <stdint.h>
 #include <string.h>

@@ -1,5 +1,5 @@
-/* p8front/p8f_stem.h -- HOST FRONT END of the paq8 stage (product code; tables are recorded through p8f_emit.h, the device learns). Word (reference src/models/paq8.cpp:1545-1622) and the stemmers'
- * interface shared by p8f_stem.c and the models that use them. */
+/* p8front/p8f_stem.h -- HOST FRONT END of the paq8 stage (product code; the oracle builds the same files). Word (reference
+ * src/models/paq8.cpp:1545-1622) and the stemmers' interface shared by p8f_stem.c and the models that use them. */
 #ifndef CMX_P8F_STEM_H
 #define CMX_P8F_STEM_H
 #include <stdint.h>

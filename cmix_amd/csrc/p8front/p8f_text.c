@@ -1,10 +1,12 @@
 /* p8front/p8f_text.c -- HOST FRONT END of the paq8 stage (product code; tables are recorded through p8f_emit.h, the device learns).
+ * One text, two back ends: the oracle's Makefile builds this same file a second time, with the p8f_* calls below mapped onto its CPU learners
+ * (paq8_names.h there), so the class-level tests against the unmodified reference pin the text that ships.
  *
  * Host front end for paq8's TextModel (reference src/models/paq8.cpp:3006-3518): a parser over the byte stream that
  * tracks words (stemmed in English, French and German at once, the language with the most recognised words among
  * the last 64 wins), segments, sentences and paragraphs, numbers and their differences, quotes, nesting, punctuation
  * and a 12-deep history of ASCII groups; 33 contexts go to one ContextMap2 and eight mixer weight-set selectors are
- * derived from the same state. Parity: tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). */
+ * derived from the same state. Pinned against the reference's own class in tests/test_oracle_paq8core.py (the oracle's build of this file) and, as built for the product, by tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). */
 #include <ctype.h>
 #include <stdint.h>
 #include <stdlib.h>

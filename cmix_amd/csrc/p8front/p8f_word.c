@@ -1,9 +1,11 @@
 /* p8front/p8f_word.c -- HOST FRONT END of the paq8 stage (product code; tables are recorded through p8f_emit.h, the device learns).
+ * One text, two back ends: the oracle's Makefile builds this same file a second time, with the p8f_* calls below mapped onto its CPU learners
+ * (paq8_names.h there), so the class-level tests against the unmodified reference pin the text that ships.
  *
  * Host front end for paq8's wordModel (reference src/models/paq8.cpp:3873-4105): word / number / punctuation state
  * over the byte stream (six word hashes, hyphenation repair, first characters of lines, column context, wiki markup
  * words, the English stemmer on completed words) feeding 61 contexts into one ContextMap, and the word-level globals
- * other models read (spaces, words, wordlen, frstchar, spafdo, col ...). Parity: tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). The reference's quirks are kept as they are (the `lastLetter = 3 && ...` assignments
+ * other models read (spaces, words, wordlen, frstchar, spafdo, col ...). Pinned against the reference's own function in tests/test_oracle_paq8core.py (the oracle's build of this file) and, as built for the product, by tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). The reference's quirks are kept as they are (the `lastLetter = 3 && ...` assignments
  * inside the hyphenation test, which leave 0 or 1 in lastLetter). */
 #include <ctype.h>
 #include <stdint.h>

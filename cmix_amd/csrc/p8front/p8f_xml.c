@@ -1,10 +1,12 @@
 /* p8front/p8f_xml.c -- HOST FRONT END of the paq8 stage (product code; tables are recorded through p8f_emit.h, the device learns).
+ * One text, two back ends: the oracle's Makefile builds this same file a second time, with the p8f_* calls below mapped onto its CPU learners
+ * (paq8_names.h there), so the class-level tests against the unmodified reference pin the text that ships.
  *
  * Host front end for paq8's XMLModel (reference src/models/paq8.cpp:7823-8096): a tag-level state machine (tag names,
  * attributes, content, CDATA, comments) over a cache of the last 32 tags, content-type detection (dates, times, URLs,
  * numbers, coordinates, temperatures, ISBN), indentation tracking; four contexts per byte into one ContextMap, and the
  * Stats.XML byte other parts of paq8 read. enwik-type input is XML, so this one matters for the headline workload.
- * Parity: tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). */
+ * Pinned against the reference's own function in tests/test_oracle_paq8core.py (the oracle's build of this file) and, as built for the product, by tests/test_p8stage_host.py (stage vs columns 434..2024 of reference traces). */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>

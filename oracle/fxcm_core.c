@@ -11,7 +11,7 @@
 #include <string.h>
 
 #include "fxcm_core.h"
-#include "fxcm_tables.h"
+#include "cmx_fxcm_tables.h"
 
 int fx_squash(int d) { return d < -2047 ? 1 : d > 2047 ? 4095 : FX_SQUASH[d + 2047]; }
 int fx_stretch(int p) { return FX_STRETCH[p]; }

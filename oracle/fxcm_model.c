@@ -258,7 +258,7 @@ static int char_swap(int c) {  /* charSwap :2281-2287: undo cmix's WRT character
 static const uint8_t kFcy[128] = {['"'] = 5, ['\''] = 6, ['('] = 1, ['L'] = 4, ['P'] = 2, ['['] = 3};               /* :3680-3689 */
 static const uint8_t kFcq[128] = {['*'] = 6, ['@'] = 1, ['J'] = 3, ['L'] = 4, ['M'] = 5, ['P'] = 2, ['Q'] = 7, ['['] = 2, ['`'] = 2};  /* :3691-3700 */
 static const uint32_t kPrimes[14] = {0, 257, 251, 241, 239, 233, 229, 227, 223, 211, 199, 197, 193, 191};
-#include "fxcm_tables.h"
+#include "cmx_fxcm_tables.h"
 
 #define BUF(i) ((int)m->buffer[((uint32_t)m->pos - (uint32_t)(i)) & BMASK])
 #define BUFR(i) ((int)m->buffer[(uint32_t)(i) & BMASK])

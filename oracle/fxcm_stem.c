@@ -1,18 +1,18 @@
 /* oracle/fxcm_stem.c -- TEST INFRASTRUCTURE ONLY (never linked into the product).
  *
  * CPU restatement of fxcm's Word and EnglishStemmer (reference src/models/fxcmv1.cpp:2302-3216), a derivative of the
- * paq8 stemmer restated in oracle/paq8_stem.c (whose Word helpers it shares): word-class, suffix and prefix flags live
+ * paq8 stemmer in cmix_amd/csrc/p8front/p8f_stem.c (whose Word helpers it shares): word-class, suffix and prefix flags live
  * in three separate words; one 32-bit stem hash; more prefixes ("anti-", "dis-"); apostrophes trimmed from both ends;
  * regions end at Length(); no case folding (the model feeds lower-case letters); closed word classes (articles,
  * conjunctions, adpositions, auxiliary verbs, numbers) recognised after stemming. Word / suffix lists and the
- * per-suffix flag words are dumped from the live reference build (oracle/fxcm_stem_tables.h). Pinned against the
+ * per-suffix flag words are dumped from the live reference build (cmix_amd/csrc/cmx_fxcm_stem_tables.h). Pinned against the
  * reference's own class in tests/test_oracle_fxcmcore.py. */
 #include <ctype.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "fxcm_stem.h"
-#include "fxcm_stem_tables.h"
+#include "cmx_fxcm_stem_tables.h"
 #define COUNT(a) ((int)(sizeof(a) / sizeof((a)[0])))
 
 /* EngWordTypeFlags / ...Negation / ...Suffix :2370-2413 (bit positions are part of the hashed state) */

@@ -3,7 +3,7 @@
  * CPU restatement of the numeric building blocks of the vendored paq8 model that SURVEY.md 8(a') lists for the paq8 /
  * fxcm device stages: the two-layer int16 mixer (reference src/models/paq8.cpp:513-598 with dot_product / train
  * :403-432), APM1 (:600-621), StateMap (:623-645), StateMap32 (:645-690) and APM (:691-712). Data tables come from
- * oracle/paq8_tables.h (dumped from the reference build). Pinned against the reference's own classes, compiled from
+ * cmix_amd/csrc/p8front/p8f_tables.h (dumped from the reference build). Pinned against the reference's own classes, compiled from
  * paq8.cpp by oracle/ref_paq8core.cpp, in tests/test_oracle_paq8core.py and against tests/golden/paq8core_vectors.npz.
  *
  * Representation choices (values identical): the mixer's lazily created weight rows (unordered_map keyed by the
@@ -13,7 +13,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "paq8_tables.h"
+#include "p8f_tables.h"
 
 static int p8_squash(int d) {  /* Squash::operator() :348-352 */
   if (d > 2047) return 4095;

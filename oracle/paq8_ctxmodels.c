@@ -291,7 +291,7 @@ uint64_t orc_p8_hash5(uint64_t a, uint64_t b, uint64_t c, uint64_t d, uint64_t e
 /* ---- picModel (:3844-3864): three bit-history contexts over the bits 215 / 431 / 647 bytes back (it runs on every
  * file type); recordModel1 (:4435-4474): five small ContextMaps over byte / word distances. hist[] = the reference's
  * ring buffer (bmask + 1 bytes), pos = bytes so far. ---- */
-#include "paq8_tables.h"
+#include "p8f_tables.h"
 int orc_p8_stretch(int p);
 typedef struct { int cxt; uint16_t t[256]; } Sm16;
 static void sm16i(Sm16* s) {

@@ -10,7 +10,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "paq8_tables.h"
+#include "p8f_tables.h"
 
 int orc_p8_stretch(int p);
 #define NEX(s, k) P8_STATE[4 * (s) + (k)]

@@ -14,7 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "paq8_tables.h"
+#include "p8f_tables.h"
 
 int orc_p8_squash(int d);
 int orc_p8_stretch(int p);

@@ -19,7 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "paq8_tables.h"
+#include "p8f_tables.h"
 
 typedef struct CM2 CM2;
 typedef struct RCM RCM;

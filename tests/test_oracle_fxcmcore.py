@@ -39,7 +39,7 @@ def _bits(rng, n, p1=0.5):
 @needs_ref
 def test_tables_match_the_reference():
     """squash / stretch (float exp / log + round in the reference's constructor), ilog, dt, the six generated state
-    tables and the tables derived from them: the committed numbers (oracle/fxcm_tables.h) and the oracle's formulas
+    tables and the tables derived from them: the committed numbers (cmix_amd/csrc/cmx_fxcm_tables.h) and the oracle's formulas
     against what the reference computes at start-up."""
     L, lib = _libs()
     outs = []

@@ -1,12 +1,19 @@
-"""CPU: the paq8 stage's HOST front end (cmix_amd/csrc/p8front/p8f_{stem,text,word,xml,record,match,exe,ctxmodels,lpm}.c) is a prefix-renamed twin of the
-oracle's restatement (oracle/paq8_*.c): nothing is linked across the line, so the two can drift, and a comparison of one with the other proves
-nothing about either. Two guards (round-4 review, "What's weak" 12):
-  * the twins stay twins: comment- and prefix-normalised, the line difference of each pair may not grow past what it is today;
-  * the PRODUCT objects themselves are pinned where they can run alone: the stemmer tests of tests/test_oracle_paq8core.py, which compare the oracle with the
-    unmodified reference's classes (oracle/_ref/libcmixrefpaq8.so), run again with libcmixamd.so's p8f_* entry points in the oracle's place."""
+"""CPU: what the paq8 stage's HOST front end (cmix_amd/csrc/p8front/) shares with the oracle, and what it does not.
+  * The parsers with no learner of their own -- p8f_{stem,text,word,xml,record,exe}.c, p8f_stem.h and the four generated table headers (paq8's and fxcm's) -- exist
+    ONCE, in the product's tree. The oracle's Makefile compiles the same files a second time with their p8f_* names mapped onto its CPU learners
+    (oracle/paq8_names.h), so the class-level tests against the unmodified reference (tests/test_oracle_paq8core.py) pin the
+    text that ships. Guarded here: no second copy comes back, and both builds see <ctype.h> as the "C" locale's (the reference never calls setlocale(); a
+    difference there sits in a force-included header, where no comparison of the sources would see it).
+  * p8f_{match,lpm,ctxmodels}.c differ from oracle/paq8_{match,lpm,ctxmodels}.c in substance (the product emits records for maps that learn on the device, the
+    oracle predicts in place) and stay prefix-renamed twins: comment- and prefix-normalised, the line difference of each pair may not grow past what it is today.
+    A comparison of one twin with the other proves nothing about either; what pins them is the reference, through the host emulation's per-step hashes
+    (tests/test_p8stage_host.py) and on the device.
+  * the PRODUCT objects themselves are pinned where they can run alone: the stemmer tests of tests/test_oracle_paq8core.py run again with libcmixamd.so's p8f_*
+    entry points in the oracle's place."""
 import difflib
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -15,7 +22,10 @@ from oracle import oracle as O
 from oracle import refharness as R
 
 # pair -> the normalised line difference on the day this test was written (round 5); a change to one file that is not mirrored in the other raises it
-PAIRS = {"stem": 2, "text": 2, "word": 1, "xml": 0, "record": 0, "match": 9, "exe": 1, "ctxmodels": 30, "lpm": 15}
+PAIRS = {"match": 9, "ctxmodels": 30, "lpm": 15}
+# the files the oracle builds from the product's tree: one copy each
+SHARED = ["p8f_%s.c" % n for n in ("stem", "text", "word", "xml", "record", "exe")] + [
+    "p8f_stem.h", "p8f_tables.h", "p8f_stem_tables.h", "cmx_fxcm_tables.h", "cmx_fxcm_stem_tables.h"]
 
 
 def _norm(path, product):
@@ -36,8 +46,24 @@ def test_front_end_and_oracle_twin_have_not_drifted(name):
     assert diff <= PAIRS[name], "p8f_%s.c and oracle/paq8_%s.c differ in %d normalised lines (%d when the guard was written): mirror the change in the twin" % (name, name, diff, PAIRS[name])
 
 
+def test_shared_parser_files_exist_once():
+    """every shared file is where the product has it, and no file name under cmix_amd/csrc/ comes back under oracle/: neither under the product's name nor
+    under the name its copy had there (paq8_* / fxcm_*). A copy would drift again."""
+    product = {f for _, _, files in os.walk(os.path.join(ROOT, "cmix_amd", "csrc")) for f in files}
+    oracle = set(os.listdir(os.path.join(ROOT, "oracle")))
+    assert not [f for f in SHARED if f not in product]
+    assert not sorted(product & oracle)
+    assert not sorted({f.replace("p8f_", "paq8_").replace("cmx_fxcm_", "fxcm_") for f in SHARED} & oracle)
+
+
+def test_oracle_library_uses_no_locale_dependent_ctype():
+    """libc's tolower / isalpha / ... follow LC_CTYPE (Python calls setlocale at start-up, the reference never does) and show as __ctype_*_loc imports"""
+    out = subprocess.check_output(["nm", "-D", "--undefined-only", O.build()], text=True)
+    assert not [l for l in out.splitlines() if "__ctype_" in l]
+
+
 class _ProductAsOracle:
-    """the product library answering to the oracle's names: orc_p8_x -> p8f_x (same signatures: the files are twins)"""
+    """the product library answering to the oracle's names: orc_p8_x -> p8f_x (same signatures: one source builds both)"""
 
     def __init__(self, product, oracle):
         self._p, self._o = product, oracle
