@@ -263,3 +263,13 @@ float orc_mixnet_step(orc_mixnet* n, const float* probs, const uint64_t* sel_in,
 void orc_mixnet_set_steps(orc_mixnet* n, uint64_t steps) {
   for (int k = 0; k < ORC_N_MIX; ++k) n->mx[k]->steps = steps;
 }
+
+/* state injection: one weight of the row that `key` selects in mixer `mixer` (the row is created if the key is new, as Mix would) --
+ * the twin of the device's cmx_mixnet_debug_state_xor on region rows0 / rows1 / rows2 (tests/test_gpu_spec_chain.py). 0 = done. */
+int orc_mixnet_set_weight(orc_mixnet* n, int mixer, uint64_t key, int index, float value) {
+  if (!n || mixer < 0 || mixer >= ORC_N_MIX) return 1;
+  mixer_t* m = n->mx[mixer];
+  if (index < 0 || index >= m->n_in) return 1;
+  get_row(m, key)->w[index] = value;
+  return 0;
+}

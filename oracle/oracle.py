@@ -249,6 +249,16 @@ class MixNet:
         lib().orc_mixnet_set_steps.argtypes = [C.c_void_p, C.c_uint64]
         lib().orc_mixnet_set_steps(self.h, int(steps))
 
+    def set_weight(self, mixer, key, index, value):
+        """State injection: weight `index` of the row that `key` selects in `mixer` (created if the key is new) := the float32 `value`, exactly.
+        The twin of the device's MixNet.debug_state_xor("rows0" / "rows1" / "rows2", ...)."""
+        L = lib()
+        L.orc_mixnet_set_weight.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_float]
+        v = np.float32(value)
+        assert np.isfinite(v)
+        if L.orc_mixnet_set_weight(self.h, int(mixer), int(key), int(index), C.c_float(float(v))):
+            raise ValueError("orc_mixnet_set_weight: no weight %d in mixer %d" % (index, mixer))
+
     def close(self):
         if self.h:
             lib().orc_mixnet_destroy(self.h)
