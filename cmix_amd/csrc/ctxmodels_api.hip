@@ -36,6 +36,8 @@ struct cmx_ctxmodels {
   size_t dist_cap = 0;
   int* d_err = nullptr;
   std::vector<CtxLane> lanes;
+  bool compact = false;              // cmx_ctxmodels_create_compact: model l writes column l of a [T][>= 64] matrix
+  std::vector<CtxRegion> regions;    // every mutable array of the state in HBM (cmx_ctxmodels_state_diff's order)
 };
 
 namespace {
@@ -68,14 +70,17 @@ void cmx_ctxmodels_destroy(cmx_ctxmodels_t* h) {
   delete h;
 }
 
-cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device) {
+static cmx_ctxmodels_t* ctx_create(const uint8_t vocab[256], int device, bool compact) {
   int ndev = cmx_device_count();
   if (ndev <= 0) { cmx_set_err("cmx_ctxmodels_create: no HIP device visible (a gfx950 GPU is required)"); return nullptr; }
   if (device < 0 || device >= ndev) { cmx_set_err("cmx_ctxmodels_create: bad device index"); return nullptr; }
   if (hipSetDevice(device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return nullptr; }
   cmx_ctxmodels_t* h = new cmx_ctxmodels();
   h->device = device;
+  h->compact = compact;
   bool fail = false;
+  std::vector<CtxRegion> tabs[5];   // regions 4..8, each in lane order
+  auto tab = [&](int region, int lane, void* p, unsigned long long words) { tabs[region - 4].push_back({region, lane, (uint32_t*)p, words}); };
   auto dalloc = [&](size_t bytes, int fill_byte) -> void* {
     void* p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) { fail = true; return nullptr; }
@@ -120,6 +125,8 @@ cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device) {
     m.pred = dalloc_half(rows * 256);
     m.cnt = (uint8_t*)dalloc(rows * 256, 0);
     if (mtype == MT_DIRECTHASH) m.chk = (unsigned long long*)dalloc(rows * 8, 0);
+    tab(4, nm, m.pred, rows * 256); tab(5, nm, m.cnt, rows * 64);
+    if (m.chk) tab(6, nm, m.chk, rows * 2);
     return nm++;
   };
   auto add_indirect = [&](int ctx, int col, float delta, int run_map) {  // indirect.cpp:4-14
@@ -135,6 +142,7 @@ cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device) {
     m.size = map_size; m.size_kind = size_kind(map_size);
     m.divisor = (float)(1.0 / (200 + 0.5f));
     m.map = (uint32_t*)dalloc(map_size * 4, 0);
+    tab(7, nm, m.map, map_size);
     return nm++;
   };
 
@@ -180,6 +188,7 @@ cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device) {
     ctx_size[nc] = 1ull << (PI[i][3] * PI[i][2]);
     c.mask1 = (unsigned)(size1 - 1); c.mask = ctx_size[nc] - 1;
     c.ihash = (uint32_t*)dalloc(size1 * 4, 0);
+    tab(8, nc, c.ihash, size1);
     add_indirect(nc, col++, 400, 0);
     nc++;
   }
@@ -242,6 +251,8 @@ cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device) {
     if (d) (void)hipMemcpy(d, dt.data(), dt.size() * 4, hipMemcpyHostToDevice);
     D.divtabs = d;
   }
+  // the compact form: model l's value goes to column l (the Bracket model's column is 0 either way); configuration only, never state
+  if (compact) for (int l = 0; l < CTX_NM; ++l) L[l].col = l;
   {
     CtxLane* d = (CtxLane*)dalloc(64 * sizeof(CtxLane), 0);
     if (d) (void)hipMemcpy(d, L.data(), 64 * sizeof(CtxLane), hipMemcpyHostToDevice);
@@ -271,6 +282,9 @@ cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device) {
     delete P;
     D.persist = d;
   }
+  h->regions = {{0, -1, (uint32_t*)D.persist, sizeof(CtxPersist) / 4}, {1, -1, (uint32_t*)D.history, CTX_HISTORY / 4},
+                {2, -1, (uint32_t*)D.shared_map, CTX_SHARED / 4}, {3, -1, (uint32_t*)D.bstack, D.bstack_cap / 2}};
+  for (const auto& t : tabs) h->regions.insert(h->regions.end(), t.begin(), t.end());
   if (fail) {
     cmx_set_err("cmx_ctxmodels_create: hipMalloc failed");
     cmx_ctxmodels_destroy(h);
@@ -290,6 +304,16 @@ cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device) {
   return h;
 }
 
+cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device) { return ctx_create(vocab, device, false); }
+cmx_ctxmodels_t* cmx_ctxmodels_create_compact(const uint8_t vocab[256], int device) { return ctx_create(vocab, device, true); }
+
+// the handle's state arrays for cmx_ctxmodels_state_diff / _debug_state_xor (ctxmodels_vote.hip)
+int cmx_ctxmodels_state_view(cmx_ctxmodels_t* h, const CtxRegion** regions, int* n, int* device) {
+  if (!h || !regions || !n || !device) { cmx_set_err("cmx_ctxmodels_state_view: bad argument"); return 1; }
+  *regions = h->regions.data(); *n = (int)h->regions.size(); *device = h->device;
+  return 0;
+}
+
 static int ctxmodels_launch(cmx_ctxmodels_t* h, const uint8_t* d_bytes, size_t nbytes, float* d_probs, size_t pstride,
                             uint32_t* d_sel, void* stream, int dry = 0, int only_k = -1);
 
@@ -297,7 +321,7 @@ int cmx_ctxmodels_run(cmx_ctxmodels_t* h, const uint8_t* d_bytes, size_t nbytes,
                       uint32_t* d_sel, void* stream) {
   if (!h) { cmx_set_err("cmx_ctxmodels_run: null handle"); return 1; }
   if (nbytes == 0) return 0;
-  if (!d_bytes || !d_probs || !d_sel || pstride < CMX_N_INPUTS) { cmx_set_err("cmx_ctxmodels_run: bad argument"); return 1; }
+  if (!d_bytes || !d_probs || !d_sel || pstride < (h->compact ? (size_t)CMX_CTX_COMPACT_STRIDE : (size_t)CMX_N_INPUTS)) { cmx_set_err("cmx_ctxmodels_run: bad argument"); return 1; }
   return ctxmodels_launch(h, d_bytes, nbytes, d_probs, pstride, d_sel, stream);
 }
 

@@ -94,4 +94,9 @@ struct CtxDev {                        // passed to the kernel by value
   unsigned char vocab[256];
 };
 
+// one mutable array of a handle's state in HBM, as cmx_ctxmodels_state_diff walks them: region 0 CtxPersist, 1 history ring, 2 shared map,
+// 3 bracket stack (lane -1), then per lane 4 pred, 5 cnt, 6 chk, 7 Match map, 8 ihash
+#define CTX_REGIONS 9
+struct CtxRegion { int region, lane; uint32_t* p; unsigned long long words; };
+
 #endif

@@ -85,6 +85,8 @@ struct cmx_engine {
   int shadow = 0;                 // cmx_set_shadow: shadow mixing networks of the look-ahead pipeline, voting on every chunk
   int shadow_repair = 0;          // cmx_set_shadow_repair: repairs on the majority the pipeline may make (0 = off)
   struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t mixer = 0, row = 0, index = 0; uint32_t mask = 0; } dbg_xor;   // cmx_debug_shadow_xor
+  int ctx_shadow = 0;             // cmx_set_ctx_shadow: shadow context stages of the look-ahead pipeline, voting on every chunk
+  struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t lane = 0, index = 0; uint32_t mask = 0; } dbg_cxor;   // cmx_debug_ctx_shadow_xor
   int mode = 0;                   // 0 undecided, 1 per-bit stages built (columns from the caller), 2 look-ahead pipeline built, 3 the decoder's pipeline (late-bit protocol)
   LookAhead* la = nullptr;
   cmx_pipeline_t* late = nullptr; // mode 3: every model family on the device, bits arriving one at a time (cmx_pipeline_late_*)
@@ -323,7 +325,8 @@ int ensure_lookahead(cmx_engine* h) {
   bool ok = la->pipe && cmx_pipeline_enable_fxcm(la->pipe, h->has_dict ? h->dict.c_str() : nullptr) == 0 &&
             cmx_pipeline_enable_paq8(la->pipe) == 0 && (!h->verify || cmx_pipeline_set_verify(la->pipe, 1) == 0) &&
             (!h->shadow || cmx_pipeline_set_shadow(la->pipe, h->shadow) == 0) &&
-            (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0);
+            (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0) &&
+            (!h->ctx_shadow || cmx_pipeline_set_ctx_shadow(la->pipe, h->ctx_shadow) == 0);   // (before the pretraining below: every instance learns the dictionary)
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
   const size_t T = 8 * kLaChunk;
   for (size_t i = 0; ok && i < kLaSlots; ++i) {
@@ -354,6 +357,10 @@ int la_top_up(cmx_engine* h, bool force_tail) {
     if (h->dbg_xor.armed && la->n_sub == h->dbg_xor.after + 1) {   // (test hook) between chunk `after` and this one
       h->dbg_xor.armed = false;
       if (cmx_pipeline_debug_shadow_xor(la->pipe, h->dbg_xor.instance, h->dbg_xor.region, h->dbg_xor.mixer, h->dbg_xor.row, h->dbg_xor.index, h->dbg_xor.mask)) return 1;
+    }
+    if (h->dbg_cxor.armed && la->n_sub == h->dbg_cxor.after + 1) {   // (test hook) the same for a context-stage instance
+      h->dbg_cxor.armed = false;
+      if (cmx_pipeline_debug_ctx_shadow_xor(la->pipe, h->dbg_cxor.instance, h->dbg_cxor.region, h->dbg_cxor.lane, h->dbg_cxor.index, h->dbg_cxor.mask)) return 1;
     }
     if (cmx_pipeline_submit(la->pipe, la->data.data() + (la->submitted - la->base), n, la->d_layer0[k], la->d_p[k])) return 1;
     la->ring[k].off = la->submitted;
@@ -688,6 +695,28 @@ int cmx_shadow_report(cmx_t* h, uint64_t out[8]) {
   if (!h || !out) { cmx_set_err("cmx_shadow_report: bad argument"); return 1; }
   if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
   return cmx_pipeline_shadow_report(h->la->pipe, out);
+}
+
+// shadow context stages of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
+int cmx_set_ctx_shadow(cmx_t* h, int k) {
+  if (!h) { cmx_set_err("cmx_set_ctx_shadow: null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err("cmx_set_ctx_shadow: k must be 0, 1 or 2 shadow context stages"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_ctx_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  h->ctx_shadow = k;
+  return 0;
+}
+int cmx_ctx_shadow_report(cmx_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_ctx_shadow_report: bad argument"); return 1; }
+  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
+  return cmx_pipeline_ctx_shadow_report(h->la->pipe, out);
+}
+int cmx_debug_ctx_shadow_xor(cmx_t* h, uint64_t after_chunk, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask) {
+  if (!h) { cmx_set_err("cmx_debug_ctx_shadow_xor: null handle"); return 1; }
+  if (!h->ctx_shadow) { cmx_set_err("cmx_debug_ctx_shadow_xor: no shadow context stages are set"); return 1; }
+  if (h->la && h->la->n_sub > after_chunk + 1) { cmx_set_err("cmx_debug_ctx_shadow_xor: that chunk has been submitted already"); return 1; }
+  h->dbg_cxor.armed = true; h->dbg_cxor.after = after_chunk; h->dbg_cxor.instance = instance; h->dbg_cxor.region = region;
+  h->dbg_cxor.lane = lane; h->dbg_cxor.index = index; h->dbg_cxor.mask = xor_mask;
+  return 0;
 }
 
 // 0 undecided, 1 per-bit stages, 2 look-ahead pipeline; in mode 2 *chunks_in_flight (may be NULL) = submitted - used up

@@ -133,6 +133,12 @@ struct Slot {
   float* d_mix0 = nullptr;                             // where instance 0 wrote this chunk's mixer outputs (d_shmix[0] or the debug area)
   hipEvent_t ev_sh[2] = {nullptr, nullptr}, ev_vote = nullptr;
   bool voted = false;                                  // this slot's chunk has a vote behind it: whoever waits for ev_mix1 also waits for ev_vote
+  // shadow context stages (cmx_pipeline_set_ctx_shadow): allocated at the first begin, nothing of it otherwise
+  float* d_cxp[2] = {nullptr, nullptr};                // [8 max][64] model outputs of shadow i + 1 (compact form)
+  uint32_t* d_cxsel[2] = {nullptr, nullptr};           // [8 max][47] its selectors
+  unsigned long long* h_cxvote = nullptr;              // pinned [12]: the context vote's record as it stood behind this chunk, then the chunk's own result
+  hipEvent_t ev_cx[2] = {nullptr, nullptr}, ev_cxvote = nullptr;
+  bool cxvoted = false;                                // this slot's chunk has a context vote behind it: slot_done waits for ev_cxvote too
 };
 }  // namespace
 
@@ -182,6 +188,7 @@ struct Late {
 
 struct cmx_pipeline {
   int device = 0;
+  uint8_t vocab[256] = {};       // as given to cmx_pipeline_create (the shadow context stages are built from it later)
   Late* late = nullptr;
   bool lstm_tolerance = false;   // cmx_pipeline_set_tolerance switched the LSTM's weight update to its MFMA form
   size_t max_chunk = 0;
@@ -225,6 +232,12 @@ struct cmx_pipeline {
   uint64_t repaired_events = 0;  // chunks with a non-agreeing vote that those repairs covered (the vote's sticky record goes on counting them: [3])
   uint64_t repaired_upto = 0;    // chunks below this index had left the instances when the last repair was made
   uint64_t repair_log[CMX_REPAIR_LOG][CMX_REPAIR_WORDS] = {};   // ring of the last repairs, entry number r at [r % CMX_REPAIR_LOG]
+  int ctx_shadow = 0;            // cmx_pipeline_set_ctx_shadow: shadow context stages beside h->ctx (0 = off: nothing below exists)
+  hipStream_t s_cx[2] = {nullptr, nullptr};       // their streams (from the factory, at set_ctx_shadow: the queue budget refuses there)
+  cmx_ctxmodels_t* cx[2] = {nullptr, nullptr};    // compact handles, created at the first begin (or pretrain)
+  cmx_ctxvote_t* cxvote = nullptr;
+  uint64_t cxvote_bits = 0;      // stream bits handed to the context vote so far
+  bool pretrained = false;       // cmx_pipeline_pretrain has run: shadow context stages set after it would start untrained
   float* dbg_mix = nullptr;      // diagnosis (cmx_pipeline_debug_mix_out): the 47 mixer outputs of every bit, [bit][47], as far as dbg_mix_cap bits
   uint64_t dbg_mix_cap = 0, dbg_mix_bits = 0;
 };
@@ -251,6 +264,7 @@ static int probe_streams(cmx_pipeline* h) {
   int n = 7;
   if (h->p8) n += cmx_p8stage_streams(h->p8, q + n, 24 - n);
   for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_sh[i];   // (null entries are skipped)
+  for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_cx[i];
   const int all = cmx_overlap_probe(q, n, &h->probe_n);
   h->probe_all = all < 0 ? 0 : all;
   h->overlap = all < 0 ? -1 : all == h->probe_n ? 1 : 0;
@@ -259,8 +273,18 @@ static int probe_streams(cmx_pipeline* h) {
 
 // a slot's chunk has left the mixing network -- and, with shadows, the vote behind it
 static hipError_t slot_done(Slot& s) {
-  const hipError_t e = hipEventSynchronize(s.ev_mix1);
+  hipError_t e = hipEventSynchronize(s.ev_mix1);
+  if (e == hipSuccess && s.cxvoted) e = hipEventSynchronize(s.ev_cxvote);
   return e == hipSuccess && s.voted ? hipEventSynchronize(s.ev_vote) : e;
+}
+// What a context vote's record (cmx_ctxvote_report's eight words) says, for an error message
+static std::string ctx_vote_text(const unsigned long long r[8]) {
+  static const int kFirstCol = 2025 - 3;   // lane order: layer-0 columns 0, 1, 2, 2025..2075
+  std::string s = "context shadow vote: the " + std::to_string(r[2]) + " context-stage instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream bit " +
+                  std::to_string(r[4]) + ", " + (r[5] < 54 ? "layer-0 column " + std::to_string(r[5] < 3 ? r[5] : kFirstCol + r[5]) : "selector " + std::to_string(r[5] - 54)) + ": ";
+  if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
+  else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own stage)" : "");
+  return s + " (the stream's output is void)";
 }
 // What a vote record (cmx_vote_report's eight words) says, for an error message
 static std::string vote_text(const unsigned long long r[8]) {
@@ -352,6 +376,29 @@ static void shadow_drop(cmx_pipeline* h) {
   h->shadow = 0;
 }
 
+// everything cmx_pipeline_set_ctx_shadow and the first begin (or pretrain) behind it made
+static void ctx_shadow_drop(cmx_pipeline* h) {
+  if (!h->ctx_shadow) return;
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();
+  cmx_ctxvote_destroy(h->cxvote); h->cxvote = nullptr;
+  for (int i = 0; i < 2; ++i) {
+    cmx_ctxmodels_destroy(h->cx[i]); h->cx[i] = nullptr;
+    if (h->s_cx[i]) cmx_destroy_stream(h->s_cx[i]);
+    h->s_cx[i] = nullptr;
+  }
+  for (Slot& s : h->slot) {
+    for (float*& p : s.d_cxp) { if (p) (void)hipFree(p); p = nullptr; }
+    for (uint32_t*& p : s.d_cxsel) { if (p) (void)hipFree(p); p = nullptr; }
+    if (s.h_cxvote) (void)hipHostFree(s.h_cxvote);
+    s.h_cxvote = nullptr;
+    for (hipEvent_t* e : {&s.ev_cx[0], &s.ev_cx[1], &s.ev_cxvote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    s.cxvoted = false;
+  }
+  wg_unclaim(h, h->ctx_shadow);
+  h->ctx_shadow = 0;
+}
+
 void cmx_pipeline_destroy(cmx_pipeline_t* h) {
   if (!h) return;
   if (h->late) {
@@ -371,6 +418,7 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
     h->late = nullptr;
   }
   shadow_drop(h);
+  ctx_shadow_drop(h);
   wg_release(h);
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
@@ -414,6 +462,7 @@ cmx_pipeline_t* cmx_pipeline_create(const uint8_t vocab[256], int device, size_t
   if (max_chunk_bytes == 0 || max_chunk_bytes > (1u << 24)) { cmx_set_err("cmx_pipeline_create: bad max_chunk_bytes"); return nullptr; }
   cmx_pipeline_t* h = new cmx_pipeline();
   h->device = device;
+  if (vocab) memcpy(h->vocab, vocab, 256);
   h->max_chunk = max_chunk_bytes;
   if (cmx_device_count() > 0 && !wg_claim(h, 27 + 52 + 1, "cmx_pipeline_create")) { delete h; return nullptr; }   // mixing network, LSTM, contexts
   // every stage reports its own failure (no device, out of memory) through cmx_last_error()
@@ -628,6 +677,73 @@ int cmx_pipeline_debug_shadow_xor(cmx_pipeline_t* h, int instance, int region, u
   if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
   return cmx_mixnet_debug_state_xor(x, region, mixer, row, index, xor_mask);
 }
+// ---- shadow context stages and their vote (include/cmix_amd.h; ctxmodels_vote.hip) ----
+// Reserves here what can be refused -- k streams of the factory (the queue budget) and one resident workgroup per shadow --; the k compact handles,
+// the vote and the per-slot buffers are made at the first begin (or by pretrain, which trains every instance).
+int cmx_pipeline_set_ctx_shadow(cmx_pipeline_t* h, int k) {
+  if (!h) { cmx_set_err("cmx_pipeline_set_ctx_shadow: null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err("cmx_pipeline_set_ctx_shadow: k must be 0, 1 or 2 shadow context stages (a vote has 2 or 3 instances)"); return 1; }
+  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_ctx_shadow: only before the first chunk"); return 1; }
+  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  if (k == h->ctx_shadow) return 0;
+  if (k && h->pretrained) { cmx_set_err("cmx_pipeline_set_ctx_shadow: only before cmx_pipeline_pretrain (a shadow that missed the dictionary disagrees in the first chunk)"); return 1; }
+  ctx_shadow_drop(h);
+  if (k == 0) return probe_streams(h) < 0 ? 1 : 0;
+  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) {
+    cmx_set_err("cmx_pipeline_set_ctx_shadow: this process holds " + std::to_string(cmx_hw_queues(h->device)) + " dedicated hardware queues on device " + std::to_string(h->device) +
+                " and " + std::to_string(k) + " shadow context stage(s) need one each, the limit is " + std::to_string(CMX_MAX_HW_QUEUES));
+    return 1;
+  }
+  if (!wg_claim(h, k, "cmx_pipeline_set_ctx_shadow")) return 1;
+  h->ctx_shadow = k;
+  for (int i = 0; i < k; ++i)
+    if (cmx_make_stream(&h->s_cx[i], 0)) { ctx_shadow_drop(h); return 1; }   // (the factory has said why)
+  return probe_streams(h) < 0 ? 1 : 0;
+}
+// the first begin (or pretrain) with shadow context stages: the handles, the vote, the per-slot buffers
+static int ctx_shadow_build(cmx_pipeline* h) {
+  const size_t T = 8 * h->max_chunk;
+  h->cxvote = cmx_ctxvote_create(h->device, 1 + h->ctx_shadow);
+  if (!h->cxvote) return 1;
+  for (int i = 0; i < h->ctx_shadow; ++i) {
+    h->cx[i] = cmx_ctxmodels_create_compact(h->vocab, h->device);
+    if (!h->cx[i]) return 1;
+  }
+  bool ok = hipSetDevice(h->device) == hipSuccess;
+  for (Slot& s : h->slot) {
+    for (int i = 0; i < h->ctx_shadow; ++i)
+      ok = ok && hipMalloc((void**)&s.d_cxp[i], T * CMX_CTX_COMPACT_STRIDE * 4) == hipSuccess && hipMalloc((void**)&s.d_cxsel[i], T * CMX_N_MIXERS * 4) == hipSuccess &&
+           hipEventCreateWithFlags(&s.ev_cx[i], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&s.h_cxvote, 12 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_cxvote, hipEventDisableTiming) == hipSuccess;
+    if (ok) memset(s.h_cxvote, 0, 12 * 8);
+  }
+  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_begin: buffer allocation for the shadow context stages failed"); return 1; }
+  return 0;
+}
+int cmx_pipeline_ctx_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_pipeline_ctx_shadow_report: bad argument"); return 1; }
+  if (!h->cxvote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
+  return cmx_ctxvote_report(h->cxvote, out);
+}
+int cmx_pipeline_ctx_shadow_values(cmx_pipeline_t* h, uint32_t words[3 * CMX_CTXVOTE_COLS], uint32_t* bit) {
+  if (!h || !words) { cmx_set_err("cmx_pipeline_ctx_shadow_values: bad argument"); return 1; }
+  if (!h->cxvote) { memset(words, 0, 3 * CMX_CTXVOTE_COLS * 4); if (bit) *bit = 0; return 0; }
+  return cmx_ctxvote_values(h->cxvote, words, bit);
+}
+static cmx_ctxmodels_t* ctx_shadow_instance(cmx_pipeline* h, int i) { return i == 0 ? h->ctx : i > 0 && i <= h->ctx_shadow ? h->cx[i - 1] : nullptr; }
+int cmx_pipeline_ctx_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[16]) {
+  if (!h || !out) { cmx_set_err("cmx_pipeline_ctx_shadow_state_diff: bad argument"); return 1; }
+  cmx_ctxmodels_t *x = ctx_shadow_instance(h, a), *y = ctx_shadow_instance(h, b);
+  if (!x || !y) { cmx_set_err("cmx_pipeline_ctx_shadow_state_diff: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
+  return cmx_ctxmodels_state_diff(x, y, out);
+}
+int cmx_pipeline_debug_ctx_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask) {
+  if (!h) { cmx_set_err("cmx_pipeline_debug_ctx_shadow_xor: null handle"); return 1; }
+  cmx_ctxmodels_t* x = ctx_shadow_instance(h, instance);
+  if (!x) { cmx_set_err("cmx_pipeline_debug_ctx_shadow_xor: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
+  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_ctx_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
+  return cmx_ctxmodels_debug_state_xor(x, region, lane, index, xor_mask);
+}
 // 0 strict, 1 tolerance: not strict as soon as EITHER the mixing network or the LSTM computes in its tolerance form
 int cmx_pipeline_stage_overlap(cmx_pipeline_t* h) { return h ? h->overlap : -1; }
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t* h) { return !h ? -1 : (h->lstm_tolerance ? 1 : cmx_mixnet_mode(h->mix)); }
@@ -693,6 +809,29 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
   if (cmx_bytemodel_bits_run(h->device, s.d_ppmd, s.d_ppmd + 256, s.d_bytes, n, d_layer0 + 2076, CMX_N_INPUTS, nullptr,
                              h->s_ctx)) return 1;
   (void)hipEventRecord(s.ev_ctx1, h->s_ctx);
+  if (h->ctx_shadow) {   // ---- the same bytes on every shadow context stage, into buffers of its own; then the vote on the last shadow's stream ----
+    if (!h->cxvote && ctx_shadow_build(h)) return 1;
+    const int k = h->ctx_shadow;
+    const float* vp[3] = {d_layer0, nullptr, nullptr};
+    const uint32_t* vs[3] = {s.d_sel, nullptr, nullptr};
+    const size_t stride[3] = {CMX_N_INPUTS, CMX_CTX_COMPACT_STRIDE, CMX_CTX_COMPACT_STRIDE};
+    const int compact[3] = {0, 1, 1};
+    for (int i = 0; i < k; ++i) {
+      hipStream_t q = h->s_cx[i];
+      (void)hipStreamWaitEvent(q, s.ev_in, 0);
+      if (cmx_ctxmodels_run(h->cx[i], s.d_bytes, n, s.d_cxp[i], CMX_CTX_COMPACT_STRIDE, s.d_cxsel[i], q)) return 1;
+      (void)hipEventRecord(s.ev_cx[i], q);
+      vp[i + 1] = s.d_cxp[i]; vs[i + 1] = s.d_cxsel[i];
+    }
+    hipStream_t q = h->s_cx[k - 1];
+    (void)hipStreamWaitEvent(q, s.ev_ctx1, 0);
+    for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_cx[i], 0);
+    if (cmx_ctxvote_run(h->cxvote, vp, stride, compact, vs, 8 * n, h->cxvote_bits, s.d_bits, q)) return 1;
+    (void)hipMemcpyAsync(s.h_cxvote, cmx_ctxvote_record(h->cxvote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
+    (void)hipEventRecord(s.ev_cxvote, q);
+    s.cxvoted = true;
+    h->cxvote_bits += 8 * n;
+  }
   // ---- LSTM byte mixer ----
   (void)hipEventRecord(s.ev_lstm0, h->s_lstm);
   if (cmx_lstm_run(h->lstm, s.d_ppmd + 256, s.d_bytes, n, s.d_lstm_out, d_layer0 + 2077, CMX_N_INPUTS,
@@ -883,6 +1022,8 @@ int cmx_pipeline_pretrain(cmx_pipeline_t* h, const uint8_t* bytes, size_t n) {
   hipEvent_t ev_d = nullptr;   // the dictionary bytes are on the device before the fxcm kernels read them
   ok = ok && hipEventCreateWithFlags(&ev_d, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev_d, h->s_ctx) == hipSuccess;
   ok = ok && cmx_ctxmodels_pretrain(h->ctx, d, n, h->s_ctx) == 0;
+  if (ok && h->ctx_shadow && !h->cxvote) ok = ctx_shadow_build(h) == 0;   // every shadow context stage learns the same bytes
+  for (int i = 0; ok && i < h->ctx_shadow; ++i) ok = hipStreamWaitEvent(h->s_cx[i], ev_d, 0) == hipSuccess && cmx_ctxmodels_pretrain(h->cx[i], d, n, h->s_cx[i]) == 0;
   // fxcm and paq8 are two of models_: Predict + Perceive per dictionary bit (predictor.cpp:471-476), fxcm with the hints at their start-up
   // value 0 (:359); the rows are discarded. The three stages learn independently, so their chunks are enqueued side by side (context
   // stage on its stream, fxcm and paq8 chunk by chunk on theirs) and waited for once: the dictionary costs the slowest stage, not the sum.
@@ -899,8 +1040,10 @@ int cmx_pipeline_pretrain(cmx_pipeline_t* h, const uint8_t* bytes, size_t n) {
     if (ok && h->p8) ok = cmx_p8stage_run(h->p8, bytes + off, m, h->d_p8_scratch, 1591, h->s_p8) == 0;
   }
   ok = hipStreamSynchronize(h->s_ctx) == hipSuccess && ok;
+  for (hipStream_t q : h->s_cx) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (h->fxcm) ok = hipStreamSynchronize(h->s_fx) == hipSuccess && ok;
   if (h->p8) ok = hipStreamSynchronize(h->s_p8) == hipSuccess && ok;
+  h->pretrained = true;
   if (zpr) (void)hipFree(zpr);
   if (zex) (void)hipFree(zex);
   if (ev_d) (void)hipEventDestroy(ev_d);
@@ -1023,6 +1166,11 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
     h->failed = true;
     return 1;
   }
+  if (s.cxvoted && s.h_cxvote[3]) {   // the context-stage instances disagreed in this chunk or an earlier one (the record is sticky): no repair, the stream stops
+    cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + ctx_vote_text(s.h_cxvote));
+    h->failed = true;
+    return 1;
+  }
   if (s.voted) {
     const unsigned* shfail = (const unsigned*)(s.h_vote + 12);
     if (shfail[0] || shfail[1]) {
@@ -1066,8 +1214,15 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
   if (h->s_fx) ok = hipStreamSynchronize(h->s_fx) == hipSuccess && ok;
   if (h->p8) ok = cmx_p8stage_sync(h->p8) == 0 && ok;
   for (hipStream_t q : h->s_sh) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
+  for (hipStream_t q : h->s_cx) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (!ok) { cmx_set_err("cmx_pipeline_sync: device error"); h->failed = true; return 1; }
   if (cmx_ctxmodels_sync(h->ctx) || cmx_mixnet_sync(h->mix)) { h->failed = true; return 1; }
+  for (cmx_ctxmodels_t* c : h->cx) if (c && cmx_ctxmodels_sync(c)) { h->failed = true; return 1; }
+  if (h->cxvote) {
+    uint64_t r[8];
+    if (cmx_ctxvote_report(h->cxvote, r)) { h->failed = true; return 1; }
+    if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + ctx_vote_text(t)); h->failed = true; return 1; }
+  }
   for (cmx_mixnet_t* m : h->sh) if (m && cmx_mixnet_sync(m)) { h->failed = true; return 1; }
   if (h->vote) {
     uint64_t r[8];
@@ -1170,6 +1325,7 @@ int cmx_pipeline_late_start(cmx_pipeline_t* h, int last_bit) {
   if (h->compact) { cmx_set_err("cmx_pipeline_late_start: the stages share HIP streams (CMX_PIPELINE_STREAMS); a decoder needs every stage kernel running at once"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   if (hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_pipeline_late_start: device error"); return 1; }   // pretraining is complete
+  ctx_shadow_drop(h);
   shadow_drop(h);   // a decoder is not covered by the vote (include/cmix_amd.h): it holds no stream, workgroup or buffer of it
   Late* L = new Late();
   h->late = L;

@@ -190,6 +190,28 @@ def lib():
         L.cmx_repair_text.restype = C.c_char_p
         L.cmx_repair_text.argtypes = [C.c_void_p]
         L.cmx_debug_shadow_xor.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
+        L.cmx_ctxmodels_create_compact.restype = C.c_void_p
+        L.cmx_ctxmodels_create_compact.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_ctxmodels_state_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_ctxmodels_debug_state_xor.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]
+        L.cmx_ctxmodels_debug_layout.argtypes = [C.c_void_p]
+        L.cmx_ctxvote_create.restype = C.c_void_p
+        L.cmx_ctxvote_create.argtypes = [C.c_int, C.c_int]
+        L.cmx_ctxvote_destroy.argtypes = [C.c_void_p]
+        L.cmx_ctxvote_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.cmx_ctxvote_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_ctxvote_record.restype = C.c_void_p
+        L.cmx_ctxvote_record.argtypes = [C.c_void_p]
+        L.cmx_ctxvote_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_ctxvote_last.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_set_ctx_shadow.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_pipeline_ctx_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_ctx_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_ctx_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.cmx_pipeline_debug_ctx_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]
+        L.cmx_set_ctx_shadow.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_ctx_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_debug_ctx_shadow_xor.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]
         L.cmx_pipeline_late_start.argtypes = [C.c_void_p, C.c_int]
         L.cmx_pipeline_late_predict.restype = C.c_float
         L.cmx_pipeline_late_predict.argtypes = [C.c_void_p]
@@ -340,6 +362,92 @@ class Vote:
     def close(self):
         if getattr(self, "h", None):
             lib().cmx_vote_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# the redundant context-stage vote (include/cmix_amd.h, cmx_ctxvote_*; the rule's specification is cmix_amd.ctxvote.ctx_vote_reference)
+CTX_STATE_REGIONS = ("persist", "history", "shared_map", "bstack", "pred", "cnt", "chk", "match_map", "ihash")
+CTXVOTE_COLS = 101   # CMX_CTXVOTE_COLS: 54 model outputs in lane order (layer-0 columns SMALL_COLS), then the 47 selectors
+CTX_COMPACT_STRIDE = 64
+
+
+def _ctx_region(r):
+    return CTX_STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
+
+
+def _ctx_vote_values(fn, h, n):
+    words, bit = np.zeros(3 * CTXVOTE_COLS, np.uint32), C.c_uint32(0)
+    if fn(h, words.ctypes.data, C.byref(bit)):
+        raise CmxError(last_error())
+    return {"words": words[:CTXVOTE_COLS * n].reshape(n, CTXVOTE_COLS).copy(), "bit": int(bit.value)}
+
+
+def _ctx_state_diff(out):
+    v = [int(x) for x in out]
+    first = {"region": v[1], "lane": _opt(v[2]), "index": v[3], "a": v[4], "b": v[5]} if v[0] else None
+    return {"words": v[0], "first": first, "per_region": dict(zip(CTX_STATE_REGIONS, v[6:15])), "lane_mask": v[15], "raw": v}
+
+
+def ctx_layout():
+    """word offsets inside state region 0 (CtxPersist) of regs, br_probs, ipred, mpred, and the region's words (cmx_ctxmodels_debug_layout)"""
+    out = (C.c_uint64 * 5)()
+    if lib().cmx_ctxmodels_debug_layout(out):
+        raise CmxError(last_error())
+    return dict(zip(("regs", "br_probs", "ipred", "mpred", "words"), [int(x) for x in out]))
+
+
+class CtxVote:
+    """The context-stage vote kernel over n = 2 or 3 instances' model outputs (a CUDA [T, stride] matrix of 4-byte words: stride >= 2078 the full
+    layer-0 form, compact=True the [T, >= 64] form) and selectors [T, 47]; the record is sticky across run() calls."""
+
+    def __init__(self, n, device=0):
+        self.n = int(n)
+        self.h = lib().cmx_ctxvote_create(device, self.n)
+        if not self.h:
+            raise CmxError(last_error())
+
+    def run(self, probs, compact, sels, stream_bit0=0, bits=None, stream=None):
+        import torch
+        assert len(probs) == self.n and len(sels) == self.n and len(compact) == self.n
+        T = int(sels[0].numel()) // N_MIXERS
+        for p, s in zip(probs, sels):
+            assert p.is_cuda and s.is_cuda and p.is_contiguous() and s.is_contiguous() and p.element_size() == 4 and s.element_size() == 4
+            assert p.dim() == 2 and p.shape[0] == T and s.numel() == T * N_MIXERS
+        if stream is None:
+            stream = torch.cuda.current_stream(probs[0].device).cuda_stream
+        ap = (C.c_void_p * 3)(*[p.data_ptr() for p in probs])
+        ast = (C.c_size_t * 3)(*[p.shape[1] for p in probs])
+        ac = (C.c_int * 3)(*[int(bool(c)) for c in compact])
+        asel = (C.c_void_p * 3)(*[s.data_ptr() for s in sels])
+        if lib().cmx_ctxvote_run(self.h, ap, ast, ac, asel, T, int(stream_bit0), bits.data_ptr() if bits is not None else None, C.c_void_p(stream)):
+            raise CmxError(last_error())
+
+    def report(self):
+        """as Vote.report; column = the element's c (0..53 model output in lane order, 54..100 selector c - 54). Synchronises the device."""
+        return _vote_report(lib().cmx_ctxvote_report, self.h)
+
+    def last(self):
+        """as Vote.last"""
+        out = (C.c_uint64 * 4)()
+        if lib().cmx_ctxvote_last(self.h, out):
+            raise CmxError(last_error())
+        v = [int(x) for x in out]
+        ev = v[0] != 0
+        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
+
+    def values(self):
+        """the captured bit of the first event: words [n, 101] u32, bit"""
+        return _ctx_vote_values(lib().cmx_ctxvote_values, self.h, self.n)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().cmx_ctxvote_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -573,11 +681,26 @@ SMALL_COLS = [0, 1, 2] + list(range(2025, 2076))  # layer-0 columns the ctx/smal
 class CtxModels:
     """Context plumbing + the 54 small native models of one stream on one GPU (chunk mode)."""
 
-    def __init__(self, vocab, device=0):
+    def __init__(self, vocab, device=0, compact=False):
+        """compact=True: model l writes column l of a [8N, >= 64] matrix (include/cmix_amd.h, cmx_ctxmodels_create_compact); the state is the same"""
         vocab = np.ascontiguousarray(vocab, np.uint8)
         assert vocab.size == 256
-        self.h = lib().cmx_ctxmodels_create(vocab.ctypes.data, device)
+        self.compact = bool(compact)
+        self.h = (lib().cmx_ctxmodels_create_compact if self.compact else lib().cmx_ctxmodels_create)(vocab.ctypes.data, device)
         if not self.h:
+            raise CmxError(last_error())
+
+    def state_diff(self, other):
+        """Every word of this handle's and `other`'s state in HBM compared (include/cmix_amd.h, cmx_ctxmodels_state_diff): dict words, first (region,
+        lane -- None in the regions without lanes --, index, a, b), per_region, lane_mask, raw. Synchronises the device."""
+        out = (C.c_uint64 * 16)()
+        if lib().cmx_ctxmodels_state_diff(self.h, other.h, out):
+            raise CmxError(last_error())
+        return _ctx_state_diff(out)
+
+    def debug_state_xor(self, region, lane, index, xor_mask):
+        """Test hook: XOR one state word (region: number or CTX_STATE_REGIONS name; lane None in regions 0..3), between chunks."""
+        if lib().cmx_ctxmodels_debug_state_xor(self.h, _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def close(self):
@@ -597,7 +720,7 @@ class CtxModels:
         N = int(data.numel())
         assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
         if probs is None:
-            probs = torch.full((8 * N, N_INPUTS), 0.5, dtype=torch.float32, device=data.device)
+            probs = torch.full((8 * N, CTX_COMPACT_STRIDE if self.compact else N_INPUTS), 0.5, dtype=torch.float32, device=data.device)
         if sel is None:
             sel = torch.zeros((8 * N, N_MIXERS), dtype=torch.int32, device=data.device)
         assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.shape[0] == 8 * N
@@ -834,6 +957,33 @@ class Pipeline:
     def debug_shadow_xor(self, instance, region, mixer, row, index, xor_mask):
         """Test hook: MixNet.debug_state_xor on one instance, between chunks."""
         if lib().cmx_pipeline_debug_shadow_xor(self.h, int(instance), _region(region), _u64(mixer), _u64(row), _u64(index), int(xor_mask)):
+            raise CmxError(last_error())
+
+    def set_ctx_shadow(self, k):
+        """k = 0 / 1 / 2 shadow context stages voting on every chunk's 54 columns and 47 selectors (include/cmix_amd.h): before the first chunk and
+        before pretrain; wait / fetch / sync then fail the chunk in which the instances disagree."""
+        if lib().cmx_pipeline_set_ctx_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+        self._ctx_shadow = int(k)
+
+    def ctx_shadow_report(self):
+        """as CtxVote.report (all zero while nothing was voted)"""
+        return _vote_report(lib().cmx_pipeline_ctx_shadow_report, self.h)
+
+    def ctx_shadow_values(self):
+        """as CtxVote.values"""
+        return _ctx_vote_values(lib().cmx_pipeline_ctx_shadow_values, self.h, 1 + getattr(self, "_ctx_shadow", 0))
+
+    def ctx_shadow_state_diff(self, a, b):
+        """CtxModels.state_diff of instances a and b (0 = the stream's own stage, 1.. = the shadows)"""
+        out = (C.c_uint64 * 16)()
+        if lib().cmx_pipeline_ctx_shadow_state_diff(self.h, int(a), int(b), out):
+            raise CmxError(last_error())
+        return _ctx_state_diff(out)
+
+    def debug_ctx_shadow_xor(self, instance, region, lane, index, xor_mask):
+        """Test hook: CtxModels.debug_state_xor on one instance, between chunks."""
+        if lib().cmx_pipeline_debug_ctx_shadow_xor(self.h, int(instance), _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def mixnet_mode(self):
@@ -1106,6 +1256,20 @@ class Predictor:
     def debug_shadow_xor(self, after_chunk, instance, region, mixer, row, index, xor_mask):
         """Test hook: one Pipeline.debug_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""
         if lib().cmx_debug_shadow_xor(self.h, int(after_chunk), int(instance), _region(region), _u64(mixer), _u64(row), _u64(index), int(xor_mask)):
+            raise CmxError(last_error())
+
+    def set_ctx_shadow(self, k):
+        """Shadow context stages of the look-ahead pipeline (include/cmix_amd.h, cmx_set_ctx_shadow): before the first stage_input / Predict."""
+        if lib().cmx_set_ctx_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+
+    def ctx_shadow_report(self):
+        """as CtxVote.report (all zero unless the handle compresses)"""
+        return _vote_report(lib().cmx_ctx_shadow_report, self.h)
+
+    def debug_ctx_shadow_xor(self, after_chunk, instance, region, lane, index, xor_mask):
+        """Test hook: one Pipeline.debug_ctx_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""
+        if lib().cmx_debug_ctx_shadow_xor(self.h, int(after_chunk), int(instance), _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def shadow_report(self):

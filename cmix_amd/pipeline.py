@@ -59,7 +59,7 @@ class EngineStream:
     is for a compressor (reference src/predictor.cpp:361-469), a sub-chunk of known bytes at a time. feed() enqueues;
     finish() returns the container bytes (header + arithmetic code), identical to the reference binary's file."""
 
-    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0, repair=0):
+    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0, repair=0, ctx_shadow=0):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", device_index)
@@ -85,6 +85,8 @@ class EngineStream:
         self.repair = int(repair)
         if self.repair:   # up to that many repairs on the majority (cmx_pipeline_set_shadow_repair, shadow=2 only): every sub-chunk is then waited for before its slot is reused
             self.pipe.set_shadow_repair(self.repair)
+        if ctx_shadow:   # that many shadow context stages vote on every sub-chunk's 54 columns and 47 selectors (cmx_pipeline_set_ctx_shadow): finish() raises on a disagreement
+            self.pipe.set_ctx_shadow(ctx_shadow)
         self.waited = 0
         self.pos = 0
         self.nsub = 0

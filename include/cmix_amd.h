@@ -118,6 +118,14 @@ int cmx_shadow_report(cmx_t*, uint64_t out[8]);
 int cmx_set_shadow_repair(cmx_t*, int max_repairs);
 int cmx_shadow_repairs(cmx_t*, uint64_t out[], size_t cap);
 int cmx_debug_shadow_xor(cmx_t*, uint64_t after_chunk, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask);
+/* Shadow context stages of the look-ahead pipeline (cmx_pipeline_set_ctx_shadow, k = 0 / 1 / 2): before the first cmx_stage_input or cmx_predict.
+ * cmx_predict then returns < 0 instead of a probability of a chunk in which the context-stage instances disagreed. A handle that decodes is not
+ * covered. The programs in integration/ read CMIX_CTX_SHADOW=1|2; the library reads no environment variable for it. cmx_ctx_shadow_report: as
+ * cmx_ctxvote_report. TEST HOOK cmx_debug_ctx_shadow_xor: arms ONE cmx_pipeline_debug_ctx_shadow_xor(instance, region, lane, index, xor_mask), made
+ * between chunk `after_chunk` and the next one of the look-ahead stream. */
+int cmx_set_ctx_shadow(cmx_t*, int k);
+int cmx_ctx_shadow_report(cmx_t*, uint64_t out[8]);
+int cmx_debug_ctx_shadow_xor(cmx_t*, uint64_t after_chunk, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask);
 void cmx_destroy(cmx_t*);
 
 /* ------------------------------------------------------------------------
@@ -320,7 +328,7 @@ cmx_ctxmodels_t* cmx_ctxmodels_create(const uint8_t vocab[256], int device);
 void cmx_ctxmodels_destroy(cmx_ctxmodels_t*);
 /* Chunk mode over nbytes already-known bytes. DEVICE pointers:
  *   d_bytes [nbytes]            u8   the bytes coded
- *   d_probs [8*nbytes][pstride] f32  the layer-0 matrix the mixing network reads (pstride >= 2078);
+ *   d_probs [8*nbytes][pstride] f32  the layer-0 matrix the mixing network reads (pstride >= 2078; a compact handle, below: >= 64);
  *                                    OUT: columns 0,1,2 and 2025..2075 of every row (Model::Predict of
  *                                    the 54 models); other columns untouched
  *   d_sel   [8*nbytes][47]      u32  OUT: every mixer's selector at each Predict() (entry 12 = 0: the
@@ -347,6 +355,49 @@ int cmx_ctxmodels_debug_set_history(cmx_ctxmodels_t*, uint64_t pos, const uint8_
 int cmx_ctxmodels_sync(cmx_ctxmodels_t*);
 /* Test hook: ContextManager registers (25), byte contexts (54), bit contexts (8) between bytes. */
 int cmx_ctxmodels_get_manager(cmx_ctxmodels_t*, uint64_t* regs25, uint64_t* ctx54, uint64_t* bitctx8);
+/* THE COMPACT FORM of a handle (for redundant instances, below): model l = 0..53 (lane order: layer-0 columns 0, 1, 2, 2025..2075) writes column l
+ * of d_probs, and cmx_ctxmodels_run accepts pstride >= CMX_CTX_COMPACT_STRIDE. The Bracket model's column is 0 either way. Only the lane table's
+ * `col` differs: the kernel, the state, the tables and the rand() draws are those of cmx_ctxmodels_create -- a compact and a full handle over the same
+ * bytes differ in configuration, never in state. */
+#define CMX_CTX_COMPACT_STRIDE 64
+cmx_ctxmodels_t* cmx_ctxmodels_create_compact(const uint8_t vocab[256], int device);
+/* THE REDUNDANT CONTEXT-STAGE VOTE (opt-in; src/ctxmodels_vote.hip). This stage is the only producer of the 47 selectors and writes 54 layer-0
+ * columns. Verify mode compares the network's copy of a slot with the slot, and the network's vote runs every instance on the same slot: a word this
+ * stage got WRONG passes both. The complementary guard runs the unchanged stage kernel on n = 2 or 3 handles over the same bytes and compares what they
+ * wrote. A chunk of nbytes has T = nbits = 8 nbytes rows; per row and instance 101 values are compared as 32-bit WORDS, never as floats (-0.0 differs from
+ * 0.0, equal NaN patterns are equal). Elements are ordered by e = t * 101 + c: c = 0..53 the model outputs in lane order (layer-0 columns 0, 1, 2,
+ * 2025..2075), c = 54..100 selectors 0..46. Column 2076 (PPMd's bits) is not this stage's output and is not compared. The rule is cmx_vote_run's:
+ * n = 3: all equal agree, exactly two equal make the third the ODD instance, all different is NO MAJORITY; n = 2: different is no majority.
+ * cmx_ctxvote_run is asynchronous on `stream`: per instance i the DEVICE matrix d_probs[i] with row stride pstride[i] (floats), compact[i] != 0 where
+ * it has the compact form (pstride >= 64), else the full layer-0 form (pstride >= 2078, read in place: instance 0 is the stream's own stage), and its
+ * selectors d_sel[i] [T][47]. Nothing is assumed about alignment. d_bits ([T], may be NULL: captured as 0) are the coded bits. One kernel with one
+ * wavefront per row (grid-stride) and a one-wave kernel behind it that folds the chunk into the sticky DEVICE record.
+ * _report / _record / _last: exactly the eight / four words of cmx_vote_report / _record / _last, [5] (of _last: [2]) being the element's c.
+ * cmx_ctxvote_values: the capture of the first event's bit -- words[i * 101 + c] of instance i (n x 101 used) and the coded bit. Synchronises.
+ * Out of scope: REPAIR on the majority (an event stops the stream), the slot's other producers (fxcm, paq8, LSTM, PPMd), the bit and decay words,
+ * the decoder's form of the stage. */
+#define CMX_CTXVOTE_COLS 101
+typedef struct cmx_ctxvote cmx_ctxvote_t;
+cmx_ctxvote_t* cmx_ctxvote_create(int device, int n);
+void cmx_ctxvote_destroy(cmx_ctxvote_t*);
+int cmx_ctxvote_run(cmx_ctxvote_t*, const float* const* d_probs, const size_t* pstride, const int* compact, const uint32_t* const* d_sel, size_t nbits,
+                    uint64_t stream_bit0, const uint8_t* d_bits, void* stream);
+int cmx_ctxvote_report(cmx_ctxvote_t*, uint64_t out[8]);
+const unsigned long long* cmx_ctxvote_record(cmx_ctxvote_t*);
+int cmx_ctxvote_values(cmx_ctxvote_t*, uint32_t words[3 * CMX_CTXVOTE_COLS], uint32_t* bit);
+int cmx_ctxvote_last(cmx_ctxvote_t*, uint64_t out[4]);
+/* Every 32-bit word of two handles' state in HBM, compared (both on one device; a == b is refused; synchronises; reads several GB per handle: after
+ * an event and in tests, between chunks only). Regions in order: 0 CtxPersist (the registers, the Bracket model, the Indirect / Match prediction
+ * tables, the per-lane positions), 1 the history ring, 2 the shared map, 3 the bracket stack, then the per-lane tables: 4 pred, 5 cnt, 6 chk
+ * (Direct / DirectHash), 7 the Match models' map, 8 ihash (IndirectHash contexts). out[0] differing words; [1..5] the first difference in
+ * region-then-lane-then-address order: region, lane (UINT64_MAX in regions 0..3), word index within the array, the word of a, the word of b
+ * (UINT64_MAX without a difference); [6..14] the count per region; [15] bit l set: lane l has a differing table word (regions 4..8). */
+int cmx_ctxmodels_state_diff(cmx_ctxmodels_t* a, cmx_ctxmodels_t* b, uint64_t out[16]);
+/* TEST HOOK: XOR one state word (addressed as cmx_ctxmodels_state_diff reports it; lane = UINT64_MAX in regions 0..3) between chunks. Synchronises
+ * the device. A data change only: no kernel stops and no wait times out. */
+int cmx_ctxmodels_debug_state_xor(cmx_ctxmodels_t*, int region, uint64_t lane, uint64_t index, uint32_t xor_mask);
+/* TEST READOUT: word offsets inside region 0 of [0] regs (u64 each), [1] br_probs[256], [2] ipred[31][256], [3] mpred[16][256]; [4] the region's words */
+int cmx_ctxmodels_debug_layout(uint64_t out[5]);
 
 /* ------------------------------------------------------------------------
  * 2f. Stage: the vendored fxcm model = FXCM::Predict / FXCM::Perceive (src/models/fxcm.cpp:14-33) around
@@ -578,6 +629,23 @@ int cmx_pipeline_shadow_repairs(cmx_pipeline_t*, uint64_t out[], size_t cap);
 /* one entry of that log in words ("chunk 3, stream bit 6144, mixer 26, instance 0 odd, 812 state word(s) repaired, origin mixer 26"): a
  * thread-local string, valid until the thread's next call */
 const char* cmx_repair_text(const uint64_t entry[CMX_REPAIR_WORDS]);
+/* SHADOW CONTEXT STAGES (opt-in, k = 0 off / 1 / 2; before the first chunk AND before cmx_pipeline_pretrain, which must train every instance): k
+ * compact cmx_ctxmodels_t run every chunk's bytes again, each on a stream of its own (also in the reduced-stream modes of CMX_PIPELINE_STREAMS) into
+ * [T][64] / [T][47] buffers of their own, and a vote (cmx_ctxvote_*; instance 0 = the stream's own stage, read in place from the slot's layer-0
+ * rows) follows every chunk on the last shadow's stream. Reserved at the set call, refused with the reason: k streams of the queue budget
+ * (CMX_MAX_HW_QUEUES) and one resident workgroup per shadow. The handles (every table of the stage again, per shadow), the vote and the per-slot
+ * buffers are created at the first cmx_pipeline_begin (or _pretrain); k = 0 gives everything back, and with k = 0 nothing is allocated, launched or
+ * waited for. cmx_pipeline_wait / _fetch / _sync fail the chunk in which the instances first disagreed -- the message names the chunk, the stream bit,
+ * "layer-0 column C" or "selector M", and the odd instance or "no majority between 2 instances" -- and void the handle, which can still be diagnosed
+ * (_ctx_shadow_report / _values: as cmx_ctxvote_report / _values, all zero while nothing was voted; _ctx_shadow_state_diff: cmx_ctxmodels_state_diff of
+ * instances a and b, 0 = the stream's own stage) and destroyed. NO REPAIR on the majority: an event stops the stream. Coexists with _set_shadow,
+ * _set_shadow_repair and _set_verify. A handle that decodes (cmx_pipeline_late_start) drops the shadows: a decoder is not covered.
+ * _debug_ctx_shadow_xor: the test hook cmx_ctxmodels_debug_state_xor on one instance, between chunks. */
+int cmx_pipeline_set_ctx_shadow(cmx_pipeline_t*, int k);
+int cmx_pipeline_ctx_shadow_report(cmx_pipeline_t*, uint64_t out[8]);
+int cmx_pipeline_ctx_shadow_values(cmx_pipeline_t*, uint32_t words[3 * CMX_CTXVOTE_COLS], uint32_t* bit);
+int cmx_pipeline_ctx_shadow_state_diff(cmx_pipeline_t*, int a, int b, uint64_t out[16]);
+int cmx_pipeline_debug_ctx_shadow_xor(cmx_pipeline_t*, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask);
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t*);
 /* Predictor::Pretrain over n dictionary bytes (HOST pointer), before the first submit: only the stages holding
  * `models_` learn (today: contexts + small models); mixers, SSE, LSTM and PPMd are not trained (predictor.cpp:471-487). */

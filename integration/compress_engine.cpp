@@ -140,6 +140,9 @@ int main(int argc, char* argv[]) {
       if (!sha || sha[0] != '2') { fprintf(stderr, "cmix_amd: CMIX_SHADOW_REPAIR needs CMIX_SHADOW=2 (a vote of two has no majority)\n"); return 1; }
       if (cmx_pipeline_set_shadow_repair(p.pipe(), atoi(rep))) Predictor::Die();
     }
+    // CMIX_CTX_SHADOW=1|2: that many shadow context stages vote on every chunk's 54 columns and 47 selectors; a disagreement stops the program
+    const char* csh = getenv("CMIX_CTX_SHADOW");
+    if (csh && (csh[0] == '1' || csh[0] == '2') && cmx_pipeline_set_ctx_shadow(p.pipe(), csh[0] - '0')) Predictor::Die();
   }
   const double t_ready = since();
   if (enable_preprocess) preprocessor::Pretrain(&p, dictionary);

@@ -59,6 +59,9 @@ class Predictor {
       if (!sha || sha[0] != '2') { fprintf(stderr, "cmix_amd: CMIX_SHADOW_REPAIR needs CMIX_SHADOW=2 (a vote of two has no majority)\n"); exit(1); }
       if (cmx_set_shadow_repair(h_, atoi(rep))) Die();
     }
+    // CMIX_CTX_SHADOW=1|2: that many shadow context stages run beside the stream's own and vote on every chunk's 54 columns and 47 selectors (a decoder is not covered)
+    const char* csh = getenv("CMIX_CTX_SHADOW");
+    if (csh && (csh[0] == '1' || csh[0] == '2') && cmx_set_ctx_shadow(h_, csh[0] - '0')) Die();
   }
   ~Predictor() {
     uint64_t rep[2 + CMX_REPAIR_LOG * CMX_REPAIR_WORDS];   // one line per repair on the majority: none without an event
