@@ -377,6 +377,19 @@ int cmx_mixnet_spec_stats(cmx_mixnet_t* h, uint64_t out[5]) {
   return 0;
 }
 
+// How the re-runs of cmx_mixnet_spec_stats were executed (helper_role's split re-run): out[0] resolved from a mid-point candidate lane,
+// [1] second half run serially from the true mid-point. Synchronises the device.
+int cmx_mixnet_spec_rerun_stats(cmx_mixnet_t* h, uint64_t out[2]) {
+  const int fail_value = 1;
+  if (!h || !out) { set_err("cmx_mixnet_spec_rerun_stats: bad argument"); return 1; }
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipDeviceSynchronize());
+  unsigned long long st[8];
+  HIP_OK(hipMemcpy(st, (char*)h->d_xfer + offsetof(SpecXfer, stat), sizeof st, hipMemcpyDeviceToHost));
+  out[0] = st[5]; out[1] = st[6];
+  return 0;
+}
+
 // Every HIP stream of the library comes from this factory (tests/test_stream_factory.py keeps it so). HIP multiplexes a process's
 // plain streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless the environment says otherwise, and it is read once, when the
 // runtime starts: often before this library is loaded), and kernels of streams that share a queue run one after the other -- the

@@ -198,8 +198,10 @@ __device__ __forceinline__ float add4(float p, float4 v) {
 // Ordered add chain over one staged segment (n = 512, or 542 for the last one): software-
 // pipelined so the LDS reads of the next 32 terms are in flight while the current 32 are added.
 // A (mixer, segment) row is SEG = 548 floats, so reading float4 128..135 is always in bounds.
-// NB: whole batches of 32 floats in the segment (16: 512 / 542 terms; 8: 256 / 286 terms, the helpers' eight-wave split)
-template <int NB> __device__ __forceinline__ float chain_seg_n(const float* rowp, int n, float p) {
+// NB: whole batches of 32 floats in the segment (16: 512 / 542 terms; 8: 256 / 286 terms, the halves of helper_role's split re-run)
+// rowp and p may differ from lane to lane (the split re-run: two sub-chains in one instruction stream). rem_on: this lane adds the terms past
+// the whole batches; a lane with it off adds NOTHING there -- the adds are skipped under EXEC, not fed +0.0f: -0 + +0 is +0.
+template <int NB> __device__ __forceinline__ float chain_seg_n(const float* rowp, int n, float p, bool rem_on = true) {
   const float4* row = reinterpret_cast<const float4*>(__builtin_assume_aligned(rowp, 16));
   float4 a[8], b[8];
 #pragma unroll
@@ -223,12 +225,14 @@ template <int NB> __device__ __forceinline__ float chain_seg_n(const float* rowp
   }
   __builtin_amdgcn_sched_barrier(0);
   const int rem4 = (n >> 2) - NB * 8;  // 0 or 7
+  if (rem_on) {
 #pragma unroll
-  for (int i = 0; i < 7; ++i)
-    if (i < rem4) p = add4(p, a[i]);
-  if (n & 2) {                      // 542 = 135 * 4 + 2, 286 = 71 * 4 + 2
-    p = fadd(p, a[7].x);
-    p = fadd(p, a[7].y);
+    for (int i = 0; i < 7; ++i)
+      if (i < rem4) p = add4(p, a[i]);
+    if (n & 2) {                      // 542 = 135 * 4 + 2, 286 = 71 * 4 + 2
+      p = fadd(p, a[7].x);
+      p = fadd(p, a[7].y);
+    }
   }
   return p;
 }
@@ -625,8 +629,8 @@ template <bool LATE, bool JIT = false, bool VER = false> __device__ void tail_b_
 // as the products are, and the true value lies within a few dozen ulps of it (profiles/r03_spec_chain_study.txt: within +-32 ulp
 // for 96-97 % of the segments on the bench text). Wave k of a helper therefore runs segment k from the 64 consecutive floats around
 // the estimate, one per lane; when wave k-1 delivers the true start, the lane whose candidate has the same bit pattern holds the
-// exact result (same operations on the same operands), otherwise the wave re-runs the segment from the true start (the serial
-// path). Either way the value handed on is exactly the reference's (mixer.cpp:40-43), and the chain's latency drops from 2078
+// exact result (same operations on the same operands), otherwise the wave re-runs the segment from the true start (itself split
+// in two speculative halves inside the wave: helper_role's miss branch). Either way the value handed on is exactly the reference's (mixer.cpp:40-43), and the chain's latency drops from 2078
 // dependent adds to ~520 plus the re-runs.
 //
 //   block 0 (main)        wave 0 gather: waits for the 26 sums, intra-layer extra-input chain, Mixer::Perceive scalars, publishes u
@@ -688,7 +692,7 @@ template <bool LATE, bool JIT = false, bool VER = false> __device__ void helper_
   float W[KS + 1], Wn[KS + 1], xc[KS + 1], xp[KS + 1];
 #pragma unroll
   for (int k = 0; k < KS + 1; ++k) { W[k] = 0.0f; Wn[k] = 0.0f; xc[k] = 0.0f; xp[k] = 0.0f; }
-  unsigned long long n_spec = 0, n_hit = 0, n_miss = 0;
+  unsigned long long n_spec = 0, n_hit = 0, n_miss = 0, n_mid = 0, n_ser = 0;
   uint32_t cur_base = 0;
   bool f_chg = false; uint32_t f_base = 0;   // of the bit fetched last: its selector changes, and to which row (read off the serial path)
   auto failed = [&]() { return lds_poll(&H->abort) != 0; };
@@ -829,9 +833,9 @@ template <bool LATE, bool JIT = false, bool VER = false> __device__ void helper_
     if (!live) { seg_store(); break; }
     // ---- products of bit t (mixer.cpp:41: in[i] * w[i], rounded) -> LDS, f64 sum of the segment ----
     float* pr = H->prod[w];
-    double ds = 0.0;
+    double ds = 0.0, dh = 0.0;   // dh: ds after the segment's first SEGN / 2 products (a snapshot: ds itself is accumulated as before), for the split re-run
 #pragma unroll
-    for (int k = 0; k < KS; ++k) { const float p = fmul(xc[k], W[k]); pr[64 * k + lane] = p; ds += (double)p; }
+    for (int k = 0; k < KS; ++k) { const float p = fmul(xc[k], W[k]); pr[64 * k + lane] = p; ds += (double)p; if (k == KS / 2 - 1) dh = ds; }
     if (w == LASTW) { const float p = tailk ? fmul(xc[KS], W[KS]) : 0.0f; if (lane < 36) pr[SEGN + lane] = p; ds += (double)p; }   // nseg .. nseg + 5: zero pad read by chain_seg_n
 #pragma unroll
     for (int k = 0; k < KS + 1; ++k) xp[k] = xc[k];
@@ -892,7 +896,28 @@ template <bool LATE, bool JIT = false, bool VER = false> __device__ void helper_
         r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r), (int)__builtin_amdgcn_readfirstlane(__ffsll((long long)hit) - 1)));
         ++n_hit;
       } else {
-        r = chain_seg_n<16>(pr, nseg, s);          // outside the candidates: the serial path
+        // Outside the candidates: the re-run from the true start, itself split in two speculative halves INSIDE this wave (a serial re-run has all
+        // 64 lanes compute one value). Lane 0 runs the first SEGN / 2 terms from s; lanes 1..63 run the remaining terms (256, the last wave 286) from
+        // the 63 consecutive floats around the f64 estimate of the mid-point, s + the wave sum of the first-half partial sums. One instruction
+        // stream, two LDS addresses per read. Hazards:
+        //  - sub-chains of different length (the last wave's 30 terms + zero pad at nseg .. nseg + 5 belong to the second half only): lane 0 adds
+        //    nothing on the surplus steps (chain_seg_n's rem_on, an EXEC mask -- never an added +0.0f);
+        //  - the two addresses are 1024 B apart, the same LDS banks: every ds_read_b128 of this path takes a second pass. Accepted: the reads are
+        //    issued a batch ahead of the 32 dependent adds that cover them, and the helper's other waves are idle meanwhile.
+        // When a candidate lane started from the true mid-point's bit pattern its result is the segment's (same operations, same operands);
+        // otherwise the second half runs serially from the true mid-point. Either way r is the exact ordered sum; n_miss counts ONE re-run.
+        const double me = (double)s + wave_sum_f64(dh);
+        const float cand = ord2f(f2ord((float)me) + lane - 32);
+        const float h = chain_seg_n<8>(pr + (lane ? SEGN / 2 : 0), nseg - SEGN / 2, lane ? cand : s, lane != 0);
+        const float mid = bcast_lane(h, 0);
+        const unsigned long long mhit = __ballot(lane != 0 && __float_as_int(cand) == __float_as_int(mid));
+        if (mhit) {
+          r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(h), (int)__builtin_amdgcn_readfirstlane(__ffsll((long long)mhit) - 1)));
+          ++n_mid;
+        } else {
+          r = chain_seg_n<8>(pr + SEGN / 2, nseg - SEGN / 2, mid);
+          ++n_ser;
+        }
         ++n_miss;
       }
     }
@@ -914,6 +939,7 @@ template <bool LATE, bool JIT = false, bool VER = false> __device__ void helper_
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (lane == 0 && w > 0) {
     atomicAdd(&X->stat[0], n_spec); atomicAdd(&X->stat[1], n_hit); atomicAdd(&X->stat[1 + w], n_miss);   // ([2..4]: re-runs of segment 1, 2, 3)
+    atomicAdd(&X->stat[5], n_mid); atomicAdd(&X->stat[6], n_ser);                                        // (how the re-runs were executed)
   }
 }
 

@@ -91,7 +91,8 @@ struct SpecXfer {
   unsigned rowidx[CMX_SPEC_RING][32];
   unsigned changed[CMX_SPEC_RING][32];
   float xs[CMX_SPEC_RING][CMX_SPEC_XS];
-  unsigned long long stat[8];  // [0] speculative segments run, [1] of them resolved from a candidate lane, [2..4] misses of segment 1..3
+  unsigned long long stat[8];  // [0] speculative segments run, [1] of them resolved from a candidate lane, [2..4] misses of segment 1..3,
+                               //   [5] of the misses: re-runs resolved at the mid-point, [6] re-runs whose second half ran serially ([5] + [6] == [2] + [3] + [4])
 };
 #define CMX_SPEC_HEADER_BYTES (64 + 128 + 2 * 32 * 8)   /* what the host clears ahead of every launch (epochs and tags restart at 0) */
 #define CMX_SPEC_LDS_BYTES 147456  /* main workgroup: 128 KB of SSE tables + records; a helper uses 9 KB of it */

@@ -612,6 +612,15 @@ class MixNet:
         v = list(out)
         return {"segments": v[0], "hits": v[1], "reruns": v[2:5], "hit_rate": (v[1] / v[0]) if v[0] else None}
 
+    def spec_rerun_stats(self):
+        """How the re-runs of spec_stats() were executed (the split re-run): resolved from a mid-point candidate lane / second half run
+        serially from the true mid-point. mid_hits + serial_halves == sum(spec_stats()["reruns"])."""
+        out = (C.c_uint64 * 2)()
+        lib().cmx_mixnet_spec_rerun_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if lib().cmx_mixnet_spec_rerun_stats(self.h, out):
+            raise CmxError(last_error())
+        return {"mid_hits": int(out[0]), "serial_halves": int(out[1])}
+
 
 class Lstm:
     """Byte-level LSTM byte mixer stage of one stream on one GPU (chunk mode)."""

@@ -194,6 +194,11 @@ int cmx_mixnet_last_kernel_ms(cmx_mixnet_t*, float* ms);
  * start holds the reference's result, otherwise the segment is re-run). Statistics since creation: out[0] speculative segments,
  * [1] resolved from a candidate, [2..4] re-runs of segment 1 / 2 / 3. Synchronises the device. */
 int cmx_mixnet_spec_stats(cmx_mixnet_t*, uint64_t out[5]);
+/* How the re-runs were executed. A re-run is itself split in two halves inside its wave: lane 0 runs the segment's first 256 terms from
+ * the true start, lanes 1..63 the rest from 63 candidate mid-points. out[0] re-runs resolved from a mid-point candidate, [1] re-runs
+ * whose second half ran serially from the true mid-point; out[0] + out[1] == the three re-run counts of cmx_mixnet_spec_stats.
+ * Synchronises the device. */
+int cmx_mixnet_spec_rerun_stats(cmx_mixnet_t*, uint64_t out[2]);
 /* Test hook (state injection): the network as after `steps` bits of a stream -- Mixer::steps_ (mixer.cpp:58,61) of all 47 mixers. The wrap / threshold
  * fixtures of tests/golden/make_wrap_traces.py place the reference's counters the same way (oracle/ref_harness.cpp). Between chunks only. */
 int cmx_mixnet_debug_set_steps(cmx_mixnet_t*, uint64_t steps);

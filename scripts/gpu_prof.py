@@ -21,6 +21,7 @@ pr = net.profile(False)
 names = ['wait scout', 'row state + decay', 'wait the 26 sums (helpers)', 'extras chain', 'u + publish (global)',
          'tail handoff + extras upd', '-', '-', '-', '-', '-', '-', 'wait tail_done(t-1)', '-', '-', '-']
 print('speculation:', net.spec_stats())
+print('re-runs:', net.spec_rerun_stats())   # how the re-runs were executed: resolved at the mid-point / second half serial
 if int(os.environ.get('CMX_MIXNET_DBG', '0')) & 4:   # the tail's two waves
     names[6:12] = ['TAIL A: row switch + prefetch', 'TAIL A: wait slot + tail_in', 'TAIL A: layer 1 (dot + chain) + hand-over', '-', 'TAIL A: layer-1 updates', 'TAIL A: loop top + wait scout']
     names[13:16] = ['TAIL B: SSE touches + wait hand-over', 'TAIL B: layer 2 + SSE + output', 'TAIL B: layer-2 update + publish']

@@ -4,6 +4,9 @@ shard through the unmodified reference (all 2078 layer-0 inputs per bit), replay
 the orc_mix_probe hook installed, and count per candidate scheme how often a speculative segment would hit (scripts/study/spec_chain.c).
 
     python scripts/spec_chain_study.py [nbytes=8192] [segments=4] [sample_every=1]   -> profiles/r03_spec_chain_study.txt
+
+With four segments the report ends with the split re-run (profiles/r14_split_rerun_study.txt): for every segment scheme 0 misses, where the true
+mid-point (two-way) or the true quarter points (four-way) lie relative to their f64 estimates, and the dependent adds either form costs.
 """
 import ctypes as C
 import os

@@ -18,6 +18,15 @@
  *         candidates only ever hit through the bracket rule (spec_offset below). Round 4: what the helpers' waves could use instead of scheme 0.
  * Also counted per BIT (26 consecutive layer-0 mixes = the 26 helper workgroups of one bit, which the gather wave waits for together): how
  * often at least one of the 78 speculative segments misses -- a miss re-runs a 512-term chain while the other 25 helpers idle.
+ *
+ * The split re-run (four segments only): a missed segment is re-run from its true start s, and that re-run can itself be speculative INSIDE
+ * the wave that runs it -- lane 0 runs the first piece from s, the other 63 lanes run the later pieces from candidate starts centred on
+ * (double)s + the f64 sum of the products before the piece. For every segment the kernel's scheme 0 misses (true start outside -32..+31 of
+ * the estimate in the ordered-integer image) this module records the offset of the true start of every later piece from its estimate, for
+ *   two-way:  one cut at term 256, 63 candidates (-31..+31);
+ *   four-way: cuts at terms 128 / 256 / 384, 21 candidates each (-10..+10);
+ * and the dependent adds a re-run then costs: one piece, plus one more piece for every cut whose candidates miss (the piece behind it is run
+ * serially from its true start; the pieces further on keep their own candidates). The last segment's 30 extra terms ride on its last piece.
  */
 #include <math.h>
 #include <stdint.h>
@@ -50,6 +59,31 @@ static float ulpf(float x) { x = fabsf(x); if (x < 1e-30f) x = 1e-30f; return ne
 
 static float seg_run(float s, const float* x, int n) { for (int i = 0; i < n; ++i) s += x[i]; return s; }
 
+/* the split re-run of a segment scheme 0 missed: [0] two-way, [1] four-way */
+static uint64_t g_rr_n, g_rr_cut_n[2][3], g_rr_cut_hit[2][3], g_rr_hist[2][3][40], g_rr_allhit[2], g_rr_steps[2], g_rr_serial_steps;
+static void split_rerun(float s, const float* x, int n) {
+  static const int ways[2] = {2, 4}, win[2] = {31, 10};
+  g_rr_n++;
+  g_rr_serial_steps += (uint64_t)n;
+  for (int v = 0; v < 2; ++v) {
+    const int piece = 512 / ways[v];
+    float t = s; double d = (double)s;
+    int missed = 0;
+    for (int c = 1; c < ways[v]; ++c) {
+      for (int i = piece * (c - 1); i < piece * c; ++i) { t += x[i]; d += (double)x[i]; }
+      const long off = (long)f2ord(t) - (long)f2ord((float)d);
+      const long a = off < 0 ? -off : off;
+      int b = 0; while ((1L << b) <= a && b < 39) ++b;   /* 0: offset 0, b: |offset| < 2^b */
+      g_rr_hist[v][c - 1][b]++;
+      g_rr_cut_n[v][c - 1]++;
+      if (a <= win[v]) g_rr_cut_hit[v][c - 1]++; else ++missed;
+    }
+    g_rr_allhit[v] += missed == 0;
+    /* dependent adds: the pieces run one after the other are 1 + missed; the last of them carries the segment's surplus over 512 terms */
+    g_rr_steps[v] += (uint64_t)(piece * (1 + missed) + (n - 512));
+  }
+}
+
 void spec_probe(const void* mixer, const float* in, const float* w, int n_in) {
   (void)mixer;
   if (n_in != 2078) return;
@@ -76,6 +110,10 @@ void spec_probe(const void* mixer, const float* in, const float* w, int n_in) {
       g_err_hist[b]++;
       double em = fabs((double)strue - d) / ulpf((float)dmax); g_err_ulp_max_sum += em; g_err_ulp_max_sq += em * em; g_err_n++;
       g_tot[k]++;
+      if (S == 4) {
+        const long so = (long)f2ord(strue) - (long)f2ord(est);
+        if (so < -32 || so > 31) split_rerun(strue, x + edge[k], edge[k + 1] - edge[k]);
+      }
       for (int sch = 0; sch < NSCHEME; ++sch) {
         float c[64], f[64];
         if (sch == 0) {
@@ -116,7 +154,9 @@ void spec_probe(const void* mixer, const float* in, const float* w, int n_in) {
 
 void spec_config(int nseg, int sample_every) { g_nseg = nseg; g_sample_every = sample_every > 0 ? sample_every : 1; }
 void spec_reset(void) { g_calls = g_seen = g_wrong = 0; memset(g_hit, 0, sizeof g_hit); memset(g_hit_exact, 0, sizeof g_hit_exact); memset(g_tot, 0, sizeof g_tot);
-  memset(g_allhit, 0, sizeof g_allhit); g_bit_calls = g_in_bit = 0; memset(g_bit_anymiss, 0, sizeof g_bit_anymiss); memset(g_bit_misses, 0, sizeof g_bit_misses); memset(g_bit_miss_now, 0, sizeof g_bit_miss_now); memset(g_err_hist, 0, sizeof g_err_hist); g_err_ulp_max_sum = g_err_ulp_max_sq = 0; g_err_n = 0; }
+  memset(g_allhit, 0, sizeof g_allhit); g_bit_calls = g_in_bit = 0; memset(g_bit_anymiss, 0, sizeof g_bit_anymiss); memset(g_bit_misses, 0, sizeof g_bit_misses); memset(g_bit_miss_now, 0, sizeof g_bit_miss_now); memset(g_err_hist, 0, sizeof g_err_hist); g_err_ulp_max_sum = g_err_ulp_max_sq = 0; g_err_n = 0;
+  g_rr_n = g_rr_serial_steps = 0; memset(g_rr_cut_n, 0, sizeof g_rr_cut_n); memset(g_rr_cut_hit, 0, sizeof g_rr_cut_hit); memset(g_rr_hist, 0, sizeof g_rr_hist);
+  memset(g_rr_allhit, 0, sizeof g_rr_allhit); memset(g_rr_steps, 0, sizeof g_rr_steps); }
 void spec_report(FILE* f_unused) {
   (void)f_unused;
   printf("segments %d, mixes sampled %llu, wrong results among hits: %llu (must be 0: monotonicity)\n", g_nseg, (unsigned long long)g_calls, (unsigned long long)g_wrong);
@@ -133,4 +173,16 @@ void spec_report(FILE* f_unused) {
   printf("|true start - f64 estimate| in ulp(estimate), log2 buckets (0: <0.5, b: < 2^b):");
   for (int b = 0; b < 24; ++b) printf(" %llu", (unsigned long long)g_err_hist[b]);
   printf("\nsame in ulp(max |prefix|): mean %.2f rms %.2f\n", g_err_ulp_max_sum / (double)g_err_n, sqrt(g_err_ulp_max_sq / (double)g_err_n));
+  if (g_nseg == 4 && g_rr_n) {
+    static const char* wn[2] = {"two-way  (cut at 256, 63 candidates -31..+31)", "four-way (cuts at 128 / 256 / 384, 21 candidates -10..+10 each)"};
+    printf("split re-run: %llu segments missed by scheme 0 (-32..+31), %.1f dependent adds per serial re-run\n", (unsigned long long)g_rr_n, (double)g_rr_serial_steps / (double)g_rr_n);
+    for (int v = 0; v < 2; ++v) {
+      printf("  %s: all cuts in their window %.4f, dependent adds per re-run %.1f\n", wn[v], (double)g_rr_allhit[v] / (double)g_rr_n, (double)g_rr_steps[v] / (double)g_rr_n);
+      for (int c = 0; c < (v ? 3 : 1); ++c) {
+        printf("    cut at term %3d: in window %.4f; |true start of the piece - its estimate| in candidates, log2 buckets (0: 0, b: < 2^b):", (v ? 128 : 256) * (c + 1), (double)g_rr_cut_hit[v][c] / (double)g_rr_cut_n[v][c]);
+        for (int b = 0; b < 24; ++b) printf(" %llu", (unsigned long long)g_rr_hist[v][c][b]);
+        printf("\n");
+      }
+    }
+  }
 }
