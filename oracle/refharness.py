@@ -145,6 +145,13 @@ class Ref:
         return np.float32(self.lib.ref_logit(C.c_float(float(p))))
 
 
+def run_in_subprocess(script, *args):
+    """One Predictor per process: run `script` with `args` in a fresh interpreter (generators call themselves with a child flag)."""
+    import subprocess
+    import sys
+    subprocess.check_call([sys.executable, script] + [str(a) for a in args])
+
+
 def vocab_of(data: bytes):
     """Reference src/runner.cpp:88-94,196-202: all 256 below 10000 bytes."""
     v = np.zeros(256, np.uint8)

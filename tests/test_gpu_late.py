@@ -167,7 +167,7 @@ import sys, os, time
 import numpy as np
 sys.path.insert(0, {root!r})
 from cmix_amd import engine as E, synth
-payload = bytes(synth.enwik_like(1400, 4321, rich=True))
+payload = {payload}
 vocab = np.zeros(256, np.uint8); vocab[list(set(payload))] = 1
 enc_p = E.Predictor(vocab, 0)
 enc_p.stage_input(payload)
@@ -195,7 +195,16 @@ def test_decode_stream_round_trip_inside_the_library():
     """cmx_decode_stream (round 6): a stream the look-ahead engine coded, decoded from its arithmetic code alone by a fresh handle -- Decoder::Decode
     (decoder.cpp:20-39) and the Decompress loop inside the library over the decoder's form of the engine (every model family a device stage; the LSTM's
     forward block as ONE launch per truncated-BPTT block, fourteen of which this stream crosses, and three decoder's chunks of 512 bytes)."""
-    out = _run_child(_DECODE_STREAM.format(root=ROOT))
+    out = _run_child(_DECODE_STREAM.format(root=ROOT, payload="bytes(synth.enwik_like(1400, 4321, rich=True))"))
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "decode_stream_time.txt"), "a") as f:
         f.write(out)
+
+
+def test_decode_stream_round_trip_nine_symbols():
+    """the decoder's form of the LSTM's forward block at V = 9: RO = 2 rows per output workgroup, so four workgroups are full, one holds a single
+    row and three hold none (nr == 0); 250 bytes cross three truncated-BPTT blocks"""
+    payload = bytes(np.random.default_rng(9).choice(np.array([0, 9, 10, 32, 65, 97, 122, 200, 255], np.uint8), 250))
+    assert len(set(payload)) == 9
+    out = _run_child(_DECODE_STREAM.format(root=ROOT, payload=repr(payload)))
+    assert "cmx_decode_stream: 250 bytes" in out

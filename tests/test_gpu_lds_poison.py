@@ -10,8 +10,9 @@ what a call finds when it begins is controlled -- and each case runs four times:
 0x00000000 (what a fresh device tends to hold). The four runs must agree in every output word and the clean one must equal the case's
 reference -- oracle or trace of the unmodified reference, compared as the stage's own parity test compares -- because a clean run that reads
 stale LDS can itself be the wrong one. A fill that did not reach every compute unit FAILS the case (a pass would prove less than it claims).
-All shapes are ones the suite already uses. The host twins (what models LDS in tests/host/*_emul.cpp, poisoned at every run) are the
-test_poisoned_lds_* cases of tests/test_*_host.py."""
+All shapes are ones the suite already uses, but for one: the LSTM at V = 62 (tests/golden/lstm_vocab_sweep.npz), where the gate workgroup's LDS
+holds a trailing partial quad and the output workgroups a partial last row -- words no other LSTM case here has. The host twins (what models
+LDS in tests/host/*_emul.cpp, poisoned at every run) are the test_poisoned_lds_* cases of tests/test_*_host.py."""
 import numpy as np
 import pytest
 
@@ -239,6 +240,24 @@ def test_lstm_small_vocabulary(monkeypatch, fill):
         assert bits_equal(out, np.array(want)).all()
         assert bits_equal(bp.reshape(-1), np.array(wantb, np.float32)).all()
     _four_runs(fill, lambda: _run_gpu(vocab, probs, data, [1, 100, 101]), check, min_fills=5)
+
+
+def test_lstm_vocabulary_62(monkeypatch, fill):
+    """V = 62 ((V + 1) % 4 == 3: the gate rows end in a partial quad; seven output workgroups of 8 rows and one of 6), the 230 bytes of the
+    vocabulary sweep cut at 1, 100, 101, against the reference's distributions, bit predictions and arg-max symbols"""
+    from cmix_amd import engine as E
+    from test_gpu_lstm import _run_gpu
+    import make_lstm_vocab as mk
+    c = mk.load_sweep()[62]
+    _before_every(monkeypatch, E.Lstm, "run", fill)
+
+    def check(out, bp, bx):
+        bad = np.nonzero(~bits_equal(out, c["lstm"]).all(axis=1))[0]
+        assert len(bad) == 0, f"LSTM distribution differs first after byte {bad[0]}"
+        badb = np.argwhere(~bits_equal(bp, c["bitp"]))
+        assert len(badb) == 0, f"bit prediction differs first at (byte, bit) {badb[0]}"
+        assert (bx == c["ex"]).all()
+    _four_runs(fill, lambda: _run_gpu(c["vocab"], c["ppmd"], c["stream"], [1, 100, 101]), check, min_fills=5)
 
 
 # ---- contexts + small models ---------------------------------------------------------------------------------------------------
