@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "../../include/cmix_amd.h"
+#include "cmx_journal.h"
 #include "cmx_streams.h"
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
@@ -87,6 +88,15 @@ struct cmx_engine {
   struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t mixer = 0, row = 0, index = 0; uint32_t mask = 0; } dbg_xor;   // cmx_debug_shadow_xor
   int ctx_shadow = 0;             // cmx_set_ctx_shadow: shadow context stages of the look-ahead pipeline, voting on every chunk
   struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t lane = 0, index = 0; uint32_t mask = 0; } dbg_cxor;   // cmx_debug_ctx_shadow_xor
+  int journal = 0;                // cmx_set_journal: log2 of the stream journal's block (0 = off): the look-ahead pipeline's kernel, or a decoder's host-side fold
+  CmxHostJournal* hj = nullptr;   // a decoder's journal (mode 3): the p and bits words, folded on this thread bit by bit
+  std::vector<std::array<uint64_t, 3>> jr_want; bool jr_check = false;   // cmx_set_journal_check: a compressor's journal to hold the decode to
+  float hj_p = 0;                 // the p of the pending predict
+  uint64_t jr_written = 0;        // blocks cmx_journal_write_files has written
+  std::string jr_path;            // ... to this path
+  bool jr_env = false;            // the path came from CMIX_JOURNAL (cmx_create): cmx_perceive writes the completed blocks every MiB, cmx_destroy closes the files
+  bool jr_closed = false;         // cmx_journal_close_files ran
+  uint64_t jr_bits = 0;           // bits perceived since cmx_create (the MiB marks)
   int mode = 0;                   // 0 undecided, 1 per-bit stages built (columns from the caller), 2 look-ahead pipeline built, 3 the decoder's pipeline (late-bit protocol)
   LookAhead* la = nullptr;
   cmx_pipeline_t* late = nullptr; // mode 3: every model family on the device, bits arriving one at a time (cmx_pipeline_late_*)
@@ -292,6 +302,10 @@ int ensure_late(cmx_engine* h, const char* where) {
   if (!ok) { cmx_pipeline_destroy(h->late); h->late = nullptr; return 1; }   // the failing stage has set the error
   h->pre.clear();
   h->pre.shrink_to_fit();
+  if (h->journal) {   // a decoder's journal: p and bits only, folded by this thread (no decoder kernel knows of it)
+    h->hj = new CmxHostJournal();
+    h->hj->k = h->journal; h->hj->check = h->jr_check; h->hj->want = h->jr_want;
+  }
   h->mode = 3;
   h->started = true;
   return 0;
@@ -326,7 +340,9 @@ int ensure_lookahead(cmx_engine* h) {
             cmx_pipeline_enable_paq8(la->pipe) == 0 && (!h->verify || cmx_pipeline_set_verify(la->pipe, 1) == 0) &&
             (!h->shadow || cmx_pipeline_set_shadow(la->pipe, h->shadow) == 0) &&
             (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0) &&
-            (!h->ctx_shadow || cmx_pipeline_set_ctx_shadow(la->pipe, h->ctx_shadow) == 0);   // (before the pretraining below: every instance learns the dictionary)
+            (!h->ctx_shadow || cmx_pipeline_set_ctx_shadow(la->pipe, h->ctx_shadow) == 0) &&   // (before the pretraining below: every instance learns the dictionary)
+            (!h->journal || cmx_pipeline_set_journal(la->pipe, h->journal) == 0);
+  if (ok && h->jr_check) { cmx_set_err("cmx_stage_input: a journal to check against is set (cmx_set_journal_check), which covers a decoder only"); ok = false; }
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
   const size_t T = 8 * kLaChunk;
   for (size_t i = 0; ok && i < kLaSlots; ++i) {
@@ -418,9 +434,30 @@ int la_perceive(cmx_engine* h, int bit) {
 
 extern "C" {
 
+static int journal_write(cmx_engine* h, const char* path, bool all, const char* where);
+// CMIX_JOURNAL=path [CMIX_JOURNAL_LOG2=k, default 19] / CMIX_JOURNAL_CHECK=path (a decoder): read HERE and not in a shim, so that every program over a
+// cmx_t has the journal whichever shim it was compiled against (the tool exists to catch a rare event in the programs as they are deployed)
+static int journal_from_env(cmx_engine* h) {
+  const char* jr = getenv("CMIX_JOURNAL");
+  const char* jl = getenv("CMIX_JOURNAL_LOG2");
+  const char* jc = getenv("CMIX_JOURNAL_CHECK");
+  if (jc && jc[0]) { if (cmx_set_journal_check(h, jc)) return 1; }
+  else if (jr && jr[0] && cmx_set_journal(h, jl ? atoi(jl) : 19)) return 1;
+  if (jr && jr[0]) { h->jr_path = jr; h->jr_written = 0; }
+  h->jr_env = (jr && jr[0]) || (jc && jc[0]);
+  return 0;
+}
+// every MiB of a journal switched on by CMIX_JOURNAL: the blocks completed so far go to the files, so a run that is killed leaves them behind
+static int journal_mark(cmx_engine* h, const char* where) {
+  if (!h->jr_env || h->jr_path.empty() || (++h->jr_bits & ((1ull << 23) - 1))) return 0;
+  return journal_write(h, nullptr, false, where);
+}
+
 void cmx_destroy(cmx_t* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
+  // a journal switched on by the environment that the program did not close itself: the rest of it, and a checked decode's last block (nothing can be returned here)
+  if (h->jr_env && !h->jr_closed && !h->failed && cmx_journal_close_files(h)) fprintf(stderr, "cmix_amd: %s\n", cmx_last_error());
   if (h->late) (void)cmx_pipeline_late_stop(h->late);   // FIRST: a decoder's stage kernels wait for bits that will not come -- without the abort word a
                                                         // device-wide synchronisation waits for their wall-clock time-outs (30 s per chunk in flight)
   (void)hipDeviceSynchronize();
@@ -430,6 +467,7 @@ void cmx_destroy(cmx_t* h) {
   if (cmx_timing_on()) fprintf(stderr, "[cmx timing] cmx_destroy at                %.3f s (process clock); %llu bits: %.3f s inside cmx_predict, %.3f s inside cmx_perceive, %.3f s in the caller between them\n", t0,
                                h->n_calls, h->t_predict, h->t_perceive, h->t_outside);
   if (h->late) cmx_pipeline_destroy(h->late);   // unwinds the kernels of the chunk in progress first
+  delete h->hj;
   CMX_TIMING("pipeline_destroy", t0);
   delete h;
 }
@@ -445,6 +483,7 @@ cmx_t* cmx_create(const uint8_t vocab[256], const char* dict_path, int device) {
   h->device = device;
   memcpy(h->vocab, vocab, 256);
   if (dict_path) { h->dict = dict_path; h->has_dict = true; }
+  if (journal_from_env(h)) { delete h; return nullptr; }
   return h;
 }
 
@@ -479,6 +518,7 @@ float cmx_predict(cmx_t* h) {
     if (ensure_late(h, where)) return fail;
     const float p = cmx_pipeline_late_predict(h->late);
     if (p < 0) return fail;
+    h->hj_p = p;
     h->predicted = true;
     txn.ok = true;
     if (cmx_timing_on()) { h->t_predict += cmx_timing_now() - tq; h->n_calls++; if (h->t_last) h->t_outside += tq - h->t_last; }
@@ -522,7 +562,7 @@ int cmx_perceive(cmx_t* h, int bit) {
   if (!h->predicted) { cmx_set_err("cmx_perceive: no pending predict()"); return 1; }
   if (h->mode == 2) {
     Txn txn(h);
-    if (la_perceive(h, bit)) return 1;
+    if (la_perceive(h, bit) || journal_mark(h, where)) return 1;
     h->predicted = false;
     txn.ok = true;
     return 0;
@@ -531,6 +571,11 @@ int cmx_perceive(cmx_t* h, int bit) {
     const double tq = cmx_timing_on() ? cmx_timing_now() : 0;
     Txn txn(h);
     if (cmx_pipeline_late_perceive(h->late, bit)) return 1;
+    if (h->hj) {   // (a block that differs from the compressor's journal stops the decode here, before the byte this bit completes is handed out)
+      std::string err;
+      if (cmx_hostjournal_add(h->hj, h->hj_p, bit, &err)) { cmx_set_err("cmx_perceive: " + err); return 1; }
+      if (journal_mark(h, where)) return 1;
+    }
     h->predicted = false;
     txn.ok = true;
     if (cmx_timing_on()) { h->t_last = cmx_timing_now(); h->t_perceive += h->t_last - tq; }
@@ -695,6 +740,72 @@ int cmx_shadow_report(cmx_t* h, uint64_t out[8]) {
   if (!h || !out) { cmx_set_err("cmx_shadow_report: bad argument"); return 1; }
   if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
   return cmx_pipeline_shadow_report(h->la->pipe, out);
+}
+
+// ---- the stream journal of a cmx_t (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict ----
+int cmx_set_journal(cmx_t* h, int log2_block_bits) {
+  if (!h) { cmx_set_err("cmx_set_journal: null handle"); return 1; }
+  if (log2_block_bits && (log2_block_bits < CMX_JOURNAL_MIN_LOG2 || log2_block_bits > CMX_JOURNAL_MAX_LOG2)) { cmx_set_err("cmx_set_journal: log2_block_bits must be 0 (off) or 6..19"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_journal: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  if (h->jr_check && log2_block_bits != h->journal) { cmx_set_err("cmx_set_journal: a journal to check against is set (cmx_set_journal_check); its block size holds"); return 1; }
+  h->journal = log2_block_bits;
+  return 0;
+}
+int cmx_set_journal_check(cmx_t* h, const char* path) {
+  if (!h || !path) { cmx_set_err("cmx_set_journal_check: bad argument"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_journal_check: only before the first cmx_predict"); return 1; }
+  std::string err; int k = 0;
+  if (cmx_journal_load_check(path, &h->jr_want, &k, &err)) { cmx_set_err("cmx_set_journal_check: " + err); return 1; }
+  h->jr_check = true;
+  h->journal = k;   // the block size comes from the file's positions
+  return 0;
+}
+// the records [from, to) of a decoder's journal, CMX_JOURNAL_RECORD words each
+static int journal_records(cmx_engine* h, uint64_t from, uint64_t to, std::vector<uint64_t>* out) {
+  out->assign((size_t)(to - from) * CMX_JOURNAL_RECORD, 0);
+  if (to == from) return 0;
+  for (uint64_t i = from; i < to; ++i) {   // a decoder's: the position, the p word and the bits word; it has no rows and no selectors
+    uint64_t* r = out->data() + (size_t)(i - from) * CMX_JOURNAL_RECORD;
+    r[0] = h->hj->blocks[i][0]; r[1 + 130] = h->hj->blocks[i][1]; r[1 + 178] = h->hj->blocks[i][2];
+  }
+  return 0;
+}
+static int journal_write(cmx_engine* h, const char* path, bool all, const char* where) {
+  if (!h) { cmx_set_err(std::string(where) + ": null handle"); return 1; }
+  if (!h->journal) { cmx_set_err(std::string(where) + ": the journal is off (cmx_set_journal)"); return 1; }
+  if (path) {
+    if (!h->jr_path.empty() && h->jr_path != path) { cmx_set_err(std::string(where) + ": this handle's journal is being written to " + h->jr_path); return 1; }
+    if (h->jr_path.empty()) { h->jr_path = path; h->jr_written = 0; }
+  }
+  if (h->jr_path.empty()) return 0;   // (_close_files without files)
+  if (h->mode == 2 && h->la) return cmx_pipeline_journal_write_files(h->la->pipe, h->jr_path.c_str(), all ? 1 : 0);
+  uint64_t have = 0, bits_last = 0;   // blocks folded, and whether the last one is full
+  if (h->mode == 3 && h->hj) {
+    have = h->hj->blocks.size();
+    if (have) bits_last = h->hj->blocks[have - 1][0] << 3;
+  }
+  uint64_t upto = have;
+  if (!all && have && (bits_last & ((1ull << h->journal) - 1))) upto = have - 1;   // the block in progress waits for its end
+  if (upto < h->jr_written) upto = h->jr_written;
+  std::vector<uint64_t> rec;
+  if (journal_records(h, h->jr_written, upto, &rec)) return 1;
+  std::string err;
+  if (cmx_journal_append_files(h->jr_path.c_str(), rec.data(), (size_t)(upto - h->jr_written), h->jr_written == 0, &err)) { cmx_set_err(std::string(where) + ": " + err); return 1; }
+  h->jr_written = upto;
+  return 0;
+}
+int cmx_journal_write_files(cmx_t* h, const char* path) {
+  if (!path) { cmx_set_err("cmx_journal_write_files: bad argument"); return 1; }
+  return journal_write(h, path, false, "cmx_journal_write_files");
+}
+int cmx_journal_close_files(cmx_t* h) {
+  if (!h) { cmx_set_err("cmx_journal_close_files: null handle"); return 1; }
+  if (!h->journal) return 0;   // (no journal: nothing to close, so a program may call this whatever its environment says)
+  h->jr_closed = true;
+  if (journal_write(h, nullptr, true, "cmx_journal_close_files")) return 1;
+  std::string err;
+  if (h->hj && cmx_hostjournal_check_tail(h->hj, &err)) { cmx_set_err("cmx_journal_close_files: " + err); return 1; }
+  return 0;
 }
 
 // shadow context stages of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict

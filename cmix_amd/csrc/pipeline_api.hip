@@ -23,8 +23,10 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include "../../include/cmix_amd.h"
+#include "cmx_journal.h"
 #include "cmx_late.h"
 #include "cmx_streams.h"
 
@@ -139,6 +141,12 @@ struct Slot {
   unsigned long long* h_cxvote = nullptr;              // pinned [12]: the context vote's record as it stood behind this chunk, then the chunk's own result
   hipEvent_t ev_cx[2] = {nullptr, nullptr}, ev_cxvote = nullptr;
   bool cxvoted = false;                                // this slot's chunk has a context vote behind it: slot_done waits for ev_cxvote too
+  // stream journal (cmx_pipeline_set_journal): allocated at the set call, nothing of it otherwise
+  unsigned long long* d_jr = nullptr;                  // the chunk's partial records on the device
+  uint64_t* h_jr = nullptr;                            // pinned: their copy, complete when ev_jr is
+  hipEvent_t ev_jr = nullptr;
+  uint64_t jr_bit0 = 0;                                // the chunk's first stream bit
+  bool journalled = false;                             // this slot's chunk has a journal behind it: slot_done waits for ev_jr too
 };
 }  // namespace
 
@@ -240,6 +248,12 @@ struct cmx_pipeline {
   bool pretrained = false;       // cmx_pipeline_pretrain has run: shadow context stages set after it would start untrained
   float* dbg_mix = nullptr;      // diagnosis (cmx_pipeline_debug_mix_out): the 47 mixer outputs of every bit, [bit][47], as far as dbg_mix_cap bits
   uint64_t dbg_mix_cap = 0, dbg_mix_bits = 0;
+  cmx_journal_t* jr = nullptr;   // cmx_pipeline_set_journal (NULL = off: nothing below is used)
+  size_t jr_cap = 0;             // partial records a slot's pair of buffers holds
+  uint64_t jr_bits = 0;          // stream bits handed to the journal so far
+  uint64_t jr_folded = 0;        // chunks whose partial records the host has folded (in stream order)
+  std::string jr_path;           // cmx_pipeline_journal_write_files: where, and how many blocks are there already
+  uint64_t jr_written = 0;
 };
 
 namespace {
@@ -274,8 +288,31 @@ static int probe_streams(cmx_pipeline* h) {
 // a slot's chunk has left the mixing network -- and, with shadows, the vote behind it
 static hipError_t slot_done(Slot& s) {
   hipError_t e = hipEventSynchronize(s.ev_mix1);
+  if (e == hipSuccess && s.journalled) e = hipEventSynchronize(s.ev_jr);
   if (e == hipSuccess && s.cxvoted) e = hipEventSynchronize(s.ev_cxvote);
   return e == hipSuccess && s.voted ? hipEventSynchronize(s.ev_vote) : e;
+}
+// the journal's partial records of every finished chunk below `upto`, in stream order (each chunk's copy is waited for: they land in order on s_mix)
+static int journal_fold(cmx_pipeline* h, uint64_t upto) {
+  if (!h->jr) return 0;
+  if (upto > h->finished) upto = h->finished;
+  for (; h->jr_folded < upto; ++h->jr_folded) {
+    Slot& s = h->slot[h->jr_folded % kSlots];
+    if (!s.journalled) continue;
+    if (hipEventSynchronize(s.ev_jr) != hipSuccess) { cmx_set_err("stream journal: device error"); return 1; }
+    if (cmx_journal_fold(h->jr, s.h_jr, 8 * s.n, s.jr_bit0)) return 1;
+  }
+  return 0;
+}
+static void journal_drop(cmx_pipeline* h) {
+  for (Slot& s : h->slot) {
+    if (s.d_jr) (void)hipFree(s.d_jr);
+    if (s.h_jr) (void)hipHostFree(s.h_jr);
+    if (s.ev_jr) (void)hipEventDestroy(s.ev_jr);
+    s.d_jr = nullptr; s.h_jr = nullptr; s.ev_jr = nullptr; s.journalled = false;
+  }
+  cmx_journal_destroy(h->jr);
+  h->jr = nullptr; h->jr_cap = 0;
 }
 // What a context vote's record (cmx_ctxvote_report's eight words) says, for an error message
 static std::string ctx_vote_text(const unsigned long long r[8]) {
@@ -422,6 +459,7 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
   wg_release(h);
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
+  journal_drop(h);
   for (Slot& s : h->slot) {
     if (s.d_bytes) (void)hipFree(s.d_bytes);
     if (s.d_bits) (void)hipFree(s.d_bits);
@@ -780,6 +818,7 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
     cmx_set_err("cmx_pipeline_begin: device error in an earlier chunk");
     return 1;
   }
+  if (h->jr && h->chunks >= (uint64_t)kSlots && journal_fold(h, h->chunks - kSlots + 1)) return 1;   // (before the slot's pinned records are written again)
   collect(h, s);
   lap(0);
   s.n = n;
@@ -944,6 +983,13 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
   (void)hipMemcpyAsync(&s.h_fail[2], cmx_mixnet_error_flag(h->mix), 4, hipMemcpyDeviceToHost, h->s_mix);
   if (cmx_mixnet_verify_on(h->mix)) (void)hipMemcpyAsync(s.h_vrec, cmx_mixnet_verify_record(h->mix), 64, hipMemcpyDeviceToHost, h->s_mix);   // (the same for verify mode's record)
   (void)hipEventRecord(s.ev_mix1, h->s_mix);
+  if (h->jr) {   // ---- the journal of what that kernel read and wrote, behind it on its stream (after ev_mix1: the stage's timing and the vote's start are unchanged) ----
+    if (cmx_journal_enqueue(h->jr, s.d_layer0, CMX_N_INPUTS, s.d_sel, s.d_bits, d_p_out, 8 * n, h->jr_bits, s.d_jr, s.h_jr, h->jr_cap, h->s_mix)) return 1;
+    (void)hipEventRecord(s.ev_jr, h->s_mix);
+    s.jr_bit0 = h->jr_bits;
+    s.journalled = true;
+    h->jr_bits += 8 * n;
+  }
   if (h->shadow) {   // ---- the same chunk on every shadow, from the slot's own rows / selectors / bits; then the vote on the last shadow's stream ----
     const float* vp[3] = {d_p_out, nullptr, nullptr};
     const float* vm[3] = {dmix, nullptr, nullptr};
@@ -1052,6 +1098,60 @@ int cmx_pipeline_pretrain(cmx_pipeline_t* h, const uint8_t* bytes, size_t n) {
   return 0;
 }
 
+// ---- the stream journal (include/cmix_amd.h, cmx_pipeline_set_journal; journal.hip) ----
+// Everything it needs is made here, before the first chunk: the handle, and per slot a pair of partial-record buffers and an event.
+int cmx_pipeline_set_journal(cmx_pipeline_t* h, int log2_block_bits) {
+  if (!h) { cmx_set_err("cmx_pipeline_set_journal: null handle"); return 1; }
+  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_journal: only before the first chunk (a handle that decodes is not journalled)"); return 1; }
+  if (log2_block_bits && (log2_block_bits < CMX_JOURNAL_MIN_LOG2 || log2_block_bits > CMX_JOURNAL_MAX_LOG2)) {
+    cmx_set_err("cmx_pipeline_set_journal: log2_block_bits must be 0 (off) or 6..19");
+    return 1;
+  }
+  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  journal_drop(h);
+  if (!log2_block_bits) return 0;
+  h->jr = cmx_journal_create(h->device, log2_block_bits);
+  if (!h->jr) return 1;
+  h->jr_cap = ((8 * h->max_chunk) >> log2_block_bits) + 2;   // a chunk may start and end inside a block
+  const size_t bytes = h->jr_cap * CMX_JOURNAL_WORDS * sizeof(uint64_t);
+  bool ok = true;
+  for (Slot& s : h->slot) {
+    ok = ok && hipMalloc((void**)&s.d_jr, bytes) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&s.h_jr, bytes, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&s.ev_jr, hipEventDisableTiming) == hipSuccess;
+  }
+  if (!ok) { (void)hipGetLastError(); journal_drop(h); cmx_set_err("cmx_pipeline_set_journal: buffer allocation failed"); return 1; }
+  return 0;
+}
+int cmx_pipeline_journal_read(cmx_pipeline_t* h, uint64_t first, uint64_t n, uint64_t* out, uint64_t* nblocks) {
+  if (!h) { cmx_set_err("cmx_pipeline_journal_read: null handle"); return 1; }
+  if (!h->jr) { cmx_set_err("cmx_pipeline_journal_read: the journal is off (cmx_pipeline_set_journal)"); return 1; }
+  if (nblocks && cmx_journal_blocks(h->jr, nblocks)) return 1;
+  return n ? cmx_journal_read(h->jr, first, n, out) : 0;
+}
+
+int cmx_pipeline_journal_write_files(cmx_pipeline_t* h, const char* path, int final) {
+  if (!h || !path) { cmx_set_err("cmx_pipeline_journal_write_files: bad argument"); return 1; }
+  if (!h->jr) { cmx_set_err("cmx_pipeline_journal_write_files: the journal is off (cmx_pipeline_set_journal)"); return 1; }
+  if (!h->jr_path.empty() && h->jr_path != path) { cmx_set_err("cmx_pipeline_journal_write_files: this handle's journal is being written to " + h->jr_path); return 1; }
+  uint64_t have = 0;
+  if (cmx_journal_blocks(h->jr, &have)) return 1;
+  uint64_t upto = have;
+  if (!final && have) {   // the block in progress waits for its end
+    uint64_t last[CMX_JOURNAL_RECORD];
+    if (cmx_journal_read(h->jr, have - 1, 1, last)) return 1;
+    if ((last[0] << 3) & ((1ull << cmx_journal_log2(h->jr)) - 1)) upto = have - 1;
+  }
+  if (upto < h->jr_written) upto = h->jr_written;
+  std::vector<uint64_t> rec((size_t)(upto - h->jr_written) * CMX_JOURNAL_RECORD + 1);
+  if (upto > h->jr_written && cmx_journal_read(h->jr, h->jr_written, upto - h->jr_written, rec.data())) return 1;
+  std::string err;
+  if (cmx_journal_append_files(path, rec.data(), (size_t)(upto - h->jr_written), h->jr_path.empty(), &err)) { cmx_set_err("cmx_pipeline_journal_write_files: " + err); return 1; }
+  h->jr_path = path;
+  h->jr_written = upto;
+  return 0;
+}
+
 // ---- repair on the majority (include/cmix_amd.h, cmx_pipeline_set_shadow_repair) ----
 int cmx_pipeline_set_shadow_repair(cmx_pipeline_t* h, int max_repairs) {
   if (!h) { cmx_set_err("cmx_pipeline_set_shadow_repair: null handle"); return 1; }
@@ -1127,6 +1227,12 @@ static int shadow_repair(cmx_pipeline* h, uint64_t index) {
       if (!s.h_vote[8]) continue;
       ok = hipMemcpy(s.d_p, s.d_shp[0], 8 * s.n * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess;
       if (ok && s.d_mix0 != s.d_shmix[0]) ok = hipMemcpy(s.d_mix0, s.d_shmix[1], 8 * s.n * 47 * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess;
+      if (ok && h->jr && s.journalled) {   // the journal describes the p that is coded: this chunk's partial records again, from the replaced p (everything was drained above)
+        if (c < h->jr_folded) { cmx_set_err("cmx_pipeline_wait: a repaired chunk's journal had been folded already (with repair armed every chunk is waited for before its slot is reused)"); h->failed = true; return 1; }
+        Slot& w = h->slot[c % kSlots];
+        ok = cmx_journal_enqueue(h->jr, w.d_layer0, CMX_N_INPUTS, w.d_sel, w.d_bits, w.d_p, 8 * w.n, w.jr_bit0, w.d_jr, w.h_jr, h->jr_cap, h->s_mix) == 0 &&
+             hipEventRecord(w.ev_jr, h->s_mix) == hipSuccess;
+      }
     }
     ok = ok && hipDeviceSynchronize() == hipSuccess;
     if (!ok) { cmx_set_err("cmx_pipeline_wait: device error while replacing the outvoted network's outputs"); h->failed = true; return 1; }
@@ -1187,7 +1293,7 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
       return 1;
     }
   }
-  return 0;
+  return journal_fold(h, index + 1);   // (behind a repair: a repaired chunk's journal was taken again from the p that is coded)
 }
 
 // cmx_pipeline_wait(index), then the chunk's probabilities (8 x its byte count floats) into p_host. Only this chunk is waited for:
@@ -1232,6 +1338,7 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
   // the multi-workgroup kernels bound every in-launch wait: one that ran out left garbage behind, not a hang
   if (cmx_lstm_failed(h->lstm)) { cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the LSTM kernels timed out (workgroups not co-resident?): the stream's output is void"); h->failed = true; return 1; }
   if (h->fxcm && cmx_fxcm_failed(h->fxcm)) { cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the fxcm kernel timed out (workgroups not co-resident?): the stream's output is void"); h->failed = true; return 1; }
+  if (journal_fold(h, h->finished)) { h->failed = true; return 1; }
   for (Slot& s : h->slot) collect(h, s);
   if (h->last_slot >= 0) {
     Slot& s = h->slot[h->last_slot];

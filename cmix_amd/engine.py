@@ -220,6 +220,21 @@ def lib():
         L.cmx_pipeline_late_host_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_pipeline_late_debug_row.restype = C.c_void_p
         L.cmx_pipeline_late_debug_row.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_journal_create.restype = C.c_void_p
+        L.cmx_journal_create.argtypes = [C.c_int, C.c_int]
+        L.cmx_journal_destroy.argtypes = [C.c_void_p]
+        L.cmx_journal_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
+        L.cmx_journal_blocks.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_journal_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.cmx_journal_host_digest.restype = C.c_size_t
+        L.cmx_journal_host_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.c_void_p]
+        L.cmx_pipeline_set_journal.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_pipeline_journal_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_journal_write_files.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        L.cmx_set_journal.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_set_journal_check.argtypes = [C.c_void_p, C.c_char_p]
+        L.cmx_journal_write_files.argtypes = [C.c_void_p, C.c_char_p]
+        L.cmx_journal_close_files.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -478,6 +493,81 @@ def lds_fill(pattern, device=0):
     d = {k: int(out[i]) for i, k in enumerate(keys)}
     d["full"] = d["workgroups"] > 0 and d["resident"] == d["workgroups"] and d["uncovered_bytes_per_cu"] == 0
     return d
+
+
+JOURNAL_RECORD = 180   # CMX_JOURNAL_RECORD: a block's end byte position, then its 179 words (cmix_amd/journal.py)
+
+
+def _journal_records(rec):
+    """(ends [n] u64, words [n, 179] u64) of n records as the library hands them out"""
+    rec = rec.reshape(-1, JOURNAL_RECORD)
+    return rec[:, 0].copy(), rec[:, 1:].copy()
+
+
+def journal_host_digest(p, bits, stream_bit0=0, log2=19):
+    """cmx_journal_host_digest: the p and bits words of HOST values (either may be None), no device: (ends [n], p words [n], bits words [n])."""
+    p = None if p is None else np.ascontiguousarray(p, np.float32)
+    bits = None if bits is None else np.ascontiguousarray(bits, np.uint8)
+    n = len(p) if p is not None else len(bits)
+    if n == 0 or not 6 <= log2 <= 19:
+        raise CmxError("journal_host_digest: no bits, or log2 not 6..19")
+    span = ((stream_bit0 + n - 1) >> log2) - (stream_bit0 >> log2) + 1
+    out = np.zeros((span, 3), np.uint64)
+    got = lib().cmx_journal_host_digest(p.ctypes.data if p is not None else None, bits.ctypes.data if bits is not None else None, n, stream_bit0, log2, out.ctypes.data)
+    if got != span:
+        raise CmxError("cmx_journal_host_digest: %d blocks, expected %d" % (got, span))
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+
+class Journal:
+    """The stand-alone stream journal (include/cmix_amd.h, cmx_journal_*): per-block digests of rows, selectors, bits and p on the device."""
+
+    def __init__(self, device=0, log2=19):
+        self.h = lib().cmx_journal_create(device, log2)
+        if not self.h:
+            raise CmxError(last_error())
+
+    def run(self, rows, sel, bits, p, stream_bit0=0, stream=None):
+        """rows: f32 cuda [T, >= 2078] (its row stride is the ld; a column slice of a wider matrix is fine), sel int32 cuda [T, 47], bits u8 cuda [T],
+        p f32 cuda [T]; any may be None. Consecutive calls continue the stream and accumulate."""
+        T = next(len(x) for x in (rows, sel, bits, p) if x is not None)
+        ld = 0
+        if rows is not None:
+            assert rows.is_cuda and rows.dim() == 2 and rows.shape[0] == T and rows.stride(1) == 1 and rows.element_size() == 4
+            ld = rows.stride(0)
+        for x in (sel, bits, p):
+            assert x is None or (x.is_cuda and x.is_contiguous() and x.shape[0] == T)
+        assert sel is None or (sel.element_size() == 4 and sel.shape[1] == 47)
+        assert bits is None or bits.element_size() == 1
+        assert p is None or p.element_size() == 4
+        ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+        if lib().cmx_journal_run(self.h, ptr(rows), ld, ptr(sel), ptr(bits), ptr(p), T, stream_bit0, C.c_void_p(stream)):
+            raise CmxError(last_error())
+
+    def blocks(self):
+        n = C.c_uint64(0)
+        if lib().cmx_journal_blocks(self.h, C.byref(n)):
+            raise CmxError(last_error())
+        return n.value
+
+    def read(self):
+        """(ends, words [nblocks, 179]) of every block so far"""
+        n = self.blocks()
+        rec = np.zeros((n, JOURNAL_RECORD), np.uint64)
+        if n and lib().cmx_journal_read(self.h, 0, n, rec.ctypes.data):
+            raise CmxError(last_error())
+        return _journal_records(rec)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().cmx_journal_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class MixNet:
@@ -938,6 +1028,26 @@ class Pipeline:
             raise CmxError(last_error())
         self._shadow = int(k)
 
+    def set_journal(self, log2=19):
+        """The stream journal (include/cmix_amd.h, cmx_pipeline_set_journal): blocks of 2^log2 bits, 0 = off; before the first chunk."""
+        if lib().cmx_pipeline_set_journal(self.h, int(log2)):
+            raise CmxError(last_error())
+
+    def journal(self):
+        """(ends, words [nblocks, 179]) of the blocks folded so far (all of them after sync()); cmix_amd.journal reads, writes and compares them."""
+        n = C.c_uint64(0)
+        if lib().cmx_pipeline_journal_read(self.h, 0, 0, None, C.byref(n)):
+            raise CmxError(last_error())
+        rec = np.zeros((n.value, JOURNAL_RECORD), np.uint64)
+        if n.value and lib().cmx_pipeline_journal_read(self.h, 0, n.value, rec.ctypes.data, None):
+            raise CmxError(last_error())
+        return _journal_records(rec)
+
+    def journal_write_files(self, path, final=False):
+        """Append the blocks completed since the last call to `path` and `path.inputs` (final: the partial last block too, after sync())."""
+        if lib().cmx_pipeline_journal_write_files(self.h, os.fsencode(path), int(bool(final))):
+            raise CmxError(last_error())
+
     def set_shadow_repair(self, max_repairs):
         """Repair on the majority (include/cmix_amd.h, cmx_pipeline_set_shadow_repair): after set_shadow(2), before the first chunk; wait / fetch
         then repair the outvoted instance from the majority, up to max_repairs times, instead of failing the chunk. 0 = off."""
@@ -1279,6 +1389,25 @@ class Predictor:
     def debug_ctx_shadow_xor(self, after_chunk, instance, region, lane, index, xor_mask):
         """Test hook: one Pipeline.debug_ctx_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""
         if lib().cmx_debug_ctx_shadow_xor(self.h, int(after_chunk), int(instance), _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
+            raise CmxError(last_error())
+
+    def set_journal(self, log2=19):
+        """The stream journal (include/cmix_amd.h, cmx_set_journal): a compressor's handle journals every chunk on the device, a decoder's folds the p
+        and bits words on the host; before the first stage_input / Predict."""
+        if lib().cmx_set_journal(self.h, int(log2)):
+            raise CmxError(last_error())
+
+    def set_journal_check(self, path):
+        """A decoder only: hold the decode to a compressor's journal (`path`, `path.inputs`); Perceive raises at the first block that differs."""
+        if lib().cmx_set_journal_check(self.h, os.fsencode(path)):
+            raise CmxError(last_error())
+
+    def journal_write_files(self, path):
+        if lib().cmx_journal_write_files(self.h, os.fsencode(path)):
+            raise CmxError(last_error())
+
+    def journal_close_files(self):
+        if lib().cmx_journal_close_files(self.h):
             raise CmxError(last_error())
 
     def shadow_report(self):

@@ -126,6 +126,31 @@ int cmx_debug_shadow_xor(cmx_t*, uint64_t after_chunk, int instance, int region,
 int cmx_set_ctx_shadow(cmx_t*, int k);
 int cmx_ctx_shadow_report(cmx_t*, uint64_t out[8]);
 int cmx_debug_ctx_shadow_xor(cmx_t*, uint64_t after_chunk, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask);
+/* The stream journal of a cmx_t (section "Stream journal" below has the digest; log2_block_bits 0 = off, else 6..19, 19 = the reference trace's 64 KB;
+ * before the first cmx_stage_input / cmx_predict). A COMPRESSOR's handle (look-ahead mode) journals every chunk on the device
+ * (cmx_pipeline_set_journal: all 179 words per block; coexists with verify, the shadows and repair). A DECODER's handle (late-bit mode)
+ * folds the p and bits words on the calling thread, in cmx_perceive, from the p it returned and the bit it was given: no decoder kernel is involved, and
+ * its records hold zeros for the column groups and the selectors. COVERS what the final mixing network read and wrote per chunk (rows, selectors, bits,
+ * p) as they lay in device memory behind its kernel; DOES NOT COVER the network's own state, the stages' tables, pretraining, or the container's bytes.
+ * cmx_journal_write_files appends every block completed since the last call to `path` ("<end byte> <131 hex words>": 130 column groups, p -- the form
+ * oracle/ref_long_trace.cpp writes and takes as its fourth argument) and `path.inputs` ("<end byte> <48 hex words>": 47 selectors, bits), and flushes
+ * them; the first call creates or empties the files; call it as often as wanted (the programs in integration/ do every MiB), a killed run leaves the
+ * blocks written so far. cmx_journal_close_files writes the rest, the partial last block included, and -- with a journal to check against -- compares
+ * that last block and the number of blocks.
+ * cmx_set_journal_check (a decoder only): reads a compressor's `path` and `path.inputs`; the block size comes from the file's positions. cmx_perceive
+ * then compares the p and bits words at the end of every block and FAILS on the first difference -- cmx_last_error names the block, its byte range and
+ * which of the two words differs -- before the block's last byte has been handed to the caller; the handle is void from there.
+ * cmx_journal_close_files without a journal does nothing and succeeds.
+ * ENVIRONMENT: cmx_create itself reads CMIX_JOURNAL=path, CMIX_JOURNAL_LOG2=k (default 19) and CMIX_JOURNAL_CHECK=path (a decoder) -- the one switch the
+ * library takes from the environment, so that a journal can be had from any program over a cmx_t as it is deployed, whichever shim it was compiled
+ * against. It makes the cmx_set_journal / cmx_set_journal_check call (a file that cannot be read fails cmx_create), cmx_perceive then writes the
+ * completed blocks to `path` every MiB, and cmx_destroy closes the files if the program did not (a difference found only there -- a checked decode's
+ * partial last block, the block count -- can only be printed to stderr, so a program that wants it as an error calls cmx_journal_close_files first,
+ * as integration/predictor_dropin.h does). With none of the three set nothing changes. */
+int cmx_set_journal(cmx_t*, int log2_block_bits);
+int cmx_set_journal_check(cmx_t*, const char* path);
+int cmx_journal_write_files(cmx_t*, const char* path);
+int cmx_journal_close_files(cmx_t*);
 void cmx_destroy(cmx_t*);
 
 /* ------------------------------------------------------------------------
@@ -652,6 +677,21 @@ int cmx_pipeline_ctx_shadow_values(cmx_pipeline_t*, uint32_t words[3 * CMX_CTXVO
 int cmx_pipeline_ctx_shadow_state_diff(cmx_pipeline_t*, int a, int b, uint64_t out[16]);
 int cmx_pipeline_debug_ctx_shadow_xor(cmx_pipeline_t*, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask);
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t*);
+/* STREAM JOURNAL (opt-in; log2_block_bits = 0 off, the default: nothing is allocated, launched or waited for; else 6..19, 19 = the 64 KB block
+ * of oracle/ref_long_trace.cpp; before the first chunk). Behind every chunk's mixing network, on the same stream, cmx_journal's kernel digests what
+ * that network read and wrote -- the slot's layer-0 rows, selectors and bits and the caller's p[] -- into per-chunk partial records, which an
+ * asynchronous copy brings to pinned memory; the slot is not reused before that copy has landed, and the host folds the records when the slot comes
+ * round again, in cmx_pipeline_wait and in cmx_pipeline_sync. Stream bit 0 is the first submitted bit (pretraining is not journalled). Coexists
+ * with _set_verify, _set_shadow, _set_ctx_shadow and _set_shadow_repair: a chunk's records are folded behind cmx_pipeline_wait's repair, and a
+ * chunk whose p[] a repair replaced has its journal taken again from the replaced p first, so the journal describes the p that is coded (as repair
+ * itself asks, every chunk is then waited for before its slot is reused). Not available to a handle that decodes.
+ * _journal_read: *nblocks = blocks folded so far (a partial last one included; call after _sync for all of them); out (may be NULL) receives
+ * records first .. first + n - 1 as cmx_journal_read does. _journal_write_files: appends the blocks folded and complete since its last call to `path`
+ * and `path.inputs` (the two text files of cmx_journal_write_files, created or emptied by the first call) and flushes them; final != 0 (after
+ * cmx_pipeline_sync) writes the partial last block too. */
+int cmx_pipeline_set_journal(cmx_pipeline_t*, int log2_block_bits);
+int cmx_pipeline_journal_read(cmx_pipeline_t*, uint64_t first, uint64_t n, uint64_t* out, uint64_t* nblocks);
+int cmx_pipeline_journal_write_files(cmx_pipeline_t*, const char* path, int final);
 /* Predictor::Pretrain over n dictionary bytes (HOST pointer), before the first submit: only the stages holding
  * `models_` learn (today: contexts + small models); mixers, SSE, LSTM and PPMd are not trained (predictor.cpp:471-487). */
 int cmx_pipeline_pretrain(cmx_pipeline_t*, const uint8_t* bytes, size_t n);
@@ -661,6 +701,36 @@ int cmx_pipeline_last_stage_ms(cmx_pipeline_t*, float ms[3]);
 /* HIP-event time of each stage (contexts, LSTM, mixing network; ms) summed over every chunk that has finished since
  * the last reset, and the number of those chunks: call after cmx_pipeline_sync(). */
 int cmx_pipeline_stage_totals(cmx_pipeline_t*, double ms[3], uint64_t* chunks, int reset);
+
+/* ------------------------------------------------------------------------
+ * Stream journal: per-block digests of what the final mixing network reads and writes, in the form of the reference-side trace tools
+ * (oracle/ref_long_trace.cpp, oracle/ref_ctx_trace.cpp; cmix_amd/journal.py is the numpy model):
+ *   A[c] = splitmix64(c) | 1, B[i] = splitmix64(0x1000000 + i) | 1, u32(x) = the word's bit pattern; sums mod 2^64 over the bits t of a block
+ *   of 2^log2_block_bits stream bits, i = t mod 2^19:
+ *     words   0..129  column group g : sum_t sum_{c in [16 g, min(16 g + 16, 2078))} (u32(row[t][c]) + 1) * A[c] * B[i]
+ *     word    130     final p        : sum_t (u32(p[t]) + 1) * B[i]
+ *     words 131..177  selector m     : sum_t (sel[t][m] + 1) * B[i]
+ *     word    178     coded bits     : sum_t (bit[t] + 1) * B[i]
+ * B's index does not depend on the block size, so the records of the sub-blocks of a 64 KB block add up to the reference's line.
+ * _run digests nbits rows (DEVICE pointers: d_rows [nbits][ld] f32, ld even and >= 2078, 8-byte aligned; d_sel [nbits][47]; d_bits [nbits];
+ * d_p [nbits]; any of them NULL: its words are not counted) whose first is stream bit stream_bit0; consecutive calls must continue where the
+ * last one ended and accumulate. One kernel behind `stream` writes the chunk's partial records, the call waits for them and folds them on the host
+ * (wrapping adds). _blocks: blocks seen so far, a partial last one included. _read: n records from `first`, CMX_JOURNAL_RECORD words each: the
+ * block's end byte position so far, then the 179 words.
+ * cmx_journal_host_digest: the p and bits words of nbits HOST values, in plain C++ (no device): out receives, per block the range touches,
+ * {end byte position, p word, bits word}; returns the number of blocks, which is (stream_bit0 + nbits - 1 >> log2) - (stream_bit0 >> log2) + 1,
+ * or 0 for nbits = 0 / a bad log2.
+ * ------------------------------------------------------------------------ */
+#define CMX_JOURNAL_WORDS 179
+#define CMX_JOURNAL_RECORD 180
+typedef struct cmx_journal cmx_journal_t;
+cmx_journal_t* cmx_journal_create(int device, int log2_block_bits);
+int cmx_journal_run(cmx_journal_t*, const float* d_rows, size_t ld, const uint32_t* d_sel, const uint8_t* d_bits, const float* d_p, size_t nbits,
+                    uint64_t stream_bit0, void* stream);
+int cmx_journal_blocks(cmx_journal_t*, uint64_t* nblocks);
+int cmx_journal_read(cmx_journal_t*, uint64_t first, uint64_t n, uint64_t* out);
+void cmx_journal_destroy(cmx_journal_t*);
+size_t cmx_journal_host_digest(const float* p, const uint8_t* bits, size_t nbits, uint64_t stream_bit0, int log2_block_bits, uint64_t* out);
 
 /* ------------------------------------------------------------------------
  * Device libm probes (parity tests): evaluate the engine's expf / tanhf /

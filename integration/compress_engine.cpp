@@ -49,6 +49,8 @@ void CompressEngine(Predictor* P, const std::vector<uint8_t>& data, cmx_encoder_
   float* const p = (float*)cmx_host_alloc(T * sizeof(float));   // page-locked
   if (!p) Predictor::Die();
   const size_t nchunks = (N + C - 1) / C;
+  const char* journal = getenv("CMIX_JOURNAL");   // (switched on in main)
+  if (journal && !journal[0]) journal = NULL;
   auto len = [&](size_t c) { return c + 1 < nchunks ? C : N - c * C; };
   auto drain = [&](size_t c) {   // chunk c: wait, copy its probabilities back, code its bytes
     if (cmx_pipeline_fetch(P->pipe(), c, p)) Predictor::Die();   // waits for this chunk only
@@ -56,11 +58,13 @@ void CompressEngine(Predictor* P, const std::vector<uint8_t>& data, cmx_encoder_
   };
   for (size_t c = 0; c < nchunks; ++c) {
     if (c >= R) drain(c - R);   // frees slot c % R
+    if (journal && c && c % 256 == 0 && cmx_pipeline_journal_write_files(P->pipe(), journal, 0)) Predictor::Die();   // every MiB: the blocks completed so far
     if (cmx_pipeline_submit(P->pipe(), data.data() + c * C, len(c), d_layer0[c % R], d_p[c % R])) Predictor::Die();
     fprintf(stderr, "\rprogress: %.2f%%", 100.0 * (c + 1) / nchunks);
   }
   for (size_t c = nchunks > R ? nchunks - R : 0; c < nchunks; ++c) drain(c);
   if (cmx_pipeline_sync(P->pipe())) Predictor::Die();
+  if (journal && cmx_pipeline_journal_write_files(P->pipe(), journal, 1)) Predictor::Die();
   uint64_t rep[2 + CMX_REPAIR_LOG * CMX_REPAIR_WORDS];   // one line per repair on the majority (CMIX_SHADOW_REPAIR): none without an event
   if (cmx_pipeline_shadow_repairs(P->pipe(), rep, sizeof rep / sizeof rep[0])) Predictor::Die();
   for (uint64_t i = 0; i < rep[1]; ++i)
@@ -143,6 +147,10 @@ int main(int argc, char* argv[]) {
     // CMIX_CTX_SHADOW=1|2: that many shadow context stages vote on every chunk's 54 columns and 47 selectors; a disagreement stops the program
     const char* csh = getenv("CMIX_CTX_SHADOW");
     if (csh && (csh[0] == '1' || csh[0] == '2') && cmx_pipeline_set_ctx_shadow(p.pipe(), csh[0] - '0')) Predictor::Die();
+    // CMIX_JOURNAL=path [CMIX_JOURNAL_LOG2=k, default 19 = 64 KB]: per-block digests of what the mixing network read and wrote, to `path` and `path.inputs` as the run goes
+    const char* jr = getenv("CMIX_JOURNAL");
+    const char* jl = getenv("CMIX_JOURNAL_LOG2");
+    if (jr && jr[0] && cmx_pipeline_set_journal(p.pipe(), jl ? atoi(jl) : 19)) Predictor::Die();
   }
   const double t_ready = since();
   if (enable_preprocess) preprocessor::Pretrain(&p, dictionary);

@@ -62,8 +62,14 @@ class Predictor {
     // CMIX_CTX_SHADOW=1|2: that many shadow context stages run beside the stream's own and vote on every chunk's 54 columns and 47 selectors (a decoder is not covered)
     const char* csh = getenv("CMIX_CTX_SHADOW");
     if (csh && (csh[0] == '1' || csh[0] == '2') && cmx_set_ctx_shadow(h_, csh[0] - '0')) Die();
+    // CMIX_JOURNAL=path [CMIX_JOURNAL_LOG2=k, default 19 = 64 KB]: per-block digests of what the mixing network read and wrote go to `path` and `path.inputs` as the
+    // run goes (-c: all 179 words per block, from the device; -d: the p and bits words, folded on this thread). CMIX_JOURNAL_CHECK=path (-d): the decode is held to a
+    // compressor's journal block by block and stops at the first block whose p or bits word differs (the block size comes from that file). cmx_create reads the three
+    // itself (the one switch the library takes from the environment: a journal works in a program whichever shim it was compiled against); Perceive writes as it goes.
   }
   ~Predictor() {
+    // the rest of the journal, the partial last block included; with CMIX_JOURNAL_CHECK the last block and the block count are compared here (nothing without a journal)
+    if (cmx_journal_close_files(h_)) Die();
     uint64_t rep[2 + CMX_REPAIR_LOG * CMX_REPAIR_WORDS];   // one line per repair on the majority: none without an event
     if (cmx_shadow_repairs(h_, rep, sizeof rep / sizeof rep[0]) == 0)
       for (uint64_t i = 0; i < rep[1]; ++i)
