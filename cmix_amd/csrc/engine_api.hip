@@ -88,6 +88,7 @@ struct cmx_engine {
   struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t mixer = 0, row = 0, index = 0; uint32_t mask = 0; } dbg_xor;   // cmx_debug_shadow_xor
   int ctx_shadow = 0;             // cmx_set_ctx_shadow: shadow context stages of the look-ahead pipeline, voting on every chunk
   struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t lane = 0, index = 0; uint32_t mask = 0; } dbg_cxor;   // cmx_debug_ctx_shadow_xor
+  int lstm_shadow = 0;            // cmx_set_lstm_shadow: shadow LSTM stages of the look-ahead pipeline, voting on every chunk
   int journal = 0;                // cmx_set_journal: log2 of the stream journal's block (0 = off): the look-ahead pipeline's kernel, or a decoder's host-side fold
   CmxHostJournal* hj = nullptr;   // a decoder's journal (mode 3): the p and bits words, folded on this thread bit by bit
   std::vector<std::array<uint64_t, 3>> jr_want; bool jr_check = false;   // cmx_set_journal_check: a compressor's journal to hold the decode to
@@ -341,6 +342,7 @@ int ensure_lookahead(cmx_engine* h) {
             (!h->shadow || cmx_pipeline_set_shadow(la->pipe, h->shadow) == 0) &&
             (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0) &&
             (!h->ctx_shadow || cmx_pipeline_set_ctx_shadow(la->pipe, h->ctx_shadow) == 0) &&   // (before the pretraining below: every instance learns the dictionary)
+            (!h->lstm_shadow || cmx_pipeline_set_lstm_shadow(la->pipe, h->lstm_shadow) == 0) &&
             (!h->journal || cmx_pipeline_set_journal(la->pipe, h->journal) == 0);
   if (ok && h->jr_check) { cmx_set_err("cmx_stage_input: a journal to check against is set (cmx_set_journal_check), which covers a decoder only"); ok = false; }
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
@@ -820,6 +822,19 @@ int cmx_ctx_shadow_report(cmx_t* h, uint64_t out[8]) {
   if (!h || !out) { cmx_set_err("cmx_ctx_shadow_report: bad argument"); return 1; }
   if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
   return cmx_pipeline_ctx_shadow_report(h->la->pipe, out);
+}
+// shadow LSTM stages of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
+int cmx_set_lstm_shadow(cmx_t* h, int k) {
+  if (!h) { cmx_set_err("cmx_set_lstm_shadow: null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err("cmx_set_lstm_shadow: k must be 0, 1 or 2 shadow LSTM stages"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_lstm_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  h->lstm_shadow = k;
+  return 0;
+}
+int cmx_lstm_shadow_report(cmx_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_lstm_shadow_report: bad argument"); return 1; }
+  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
+  return cmx_pipeline_lstm_shadow_report(h->la->pipe, out);
 }
 int cmx_debug_ctx_shadow_xor(cmx_t* h, uint64_t after_chunk, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask) {
   if (!h) { cmx_set_err("cmx_debug_ctx_shadow_xor: null handle"); return 1; }

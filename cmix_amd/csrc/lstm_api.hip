@@ -376,4 +376,36 @@ int cmx_lstm_get_gate_weights(cmx_lstm_t* h, int layer, int gate, float* out) {
 }
 int cmx_lstm_gate_rowlen(const cmx_lstm_t* h, int layer) { return h ? h->h_state.rowlen[layer] : -1; }
 
+// The handle's state arrays for cmx_lstm_state_diff / _debug_state_xor / _debug_layout (lstm_vote.hip), in the order include/cmix_amd.h fixes:
+// out[LSTM_STATE_ARRAYS]; counters = bytes_done, hc, bptt_rounds. Not listed: sync (counters), blk (device addresses), raw / logits (no kernel
+// reads or writes them since the block kernels), OLT (null).
+int cmx_lstm_state_view(cmx_lstm_t* h, LstmRegion* out, int* n, int* device, uint64_t counters[3]) {
+  if (!h || !out || !n || !device) { cmx_set_err("cmx_lstm_state_view: bad argument"); return 1; }
+  const LstmState& S = h->h_state;
+  int k = 0;
+  auto add = [&](int region, const void* p, size_t words) { out[k].region = region; out[k].p = (uint32_t*)p; out[k].words = words; ++k; };
+  auto gates = [&](int region, float* const (&a)[LSTM_L][3], size_t w0, size_t w1) {
+    for (int l = 0; l < LSTM_L; ++l) for (int g = 0; g < 3; ++g) add(region, a[l][g], l ? w1 : w0);
+  };
+  const size_t HC = (size_t)LSTM_H * LSTM_C, w0 = (size_t)LSTM_C * S.rowlen[0], w1 = (size_t)LSTM_C * S.rowlen[1];
+  gates(0, S.W, w0, w1); gates(1, S.WT, w0, w1); gates(2, S.M, w0, w1); gates(3, S.Vv, w0, w1);
+  gates(4, S.gb, 8 * LSTM_C, 8 * LSTM_C); add(4, S.adam_tab, 4 * (LSTM_UPDATE_LIMIT + 1));
+  gates(5, S.norm, HC, HC); gates(5, S.gstate, HC, HC); gates(5, S.ivar, LSTM_H, LSTM_H); gates(5, S.E, HC, HC);
+  for (int l = 0; l < LSTM_L; ++l) add(5, S.last_state[l], HC);
+  for (int l = 0; l < LSTM_L; ++l) add(5, S.tanh_state[l], HC);
+  for (int l = 0; l < LSTM_L; ++l) add(5, S.in_gate_state[l], HC);
+  for (int b = 0; b < 2; ++b) for (int l = 0; l < LSTM_L; ++l) add(6, S.stateb[b][l], LSTM_C);
+  add(6, S.hid[0], LSTM_NH); add(6, S.hid[1], LSTM_NH);
+  for (int l = 0; l < LSTM_L; ++l) add(7, S.layer_input[l], (size_t)LSTM_H * S.insz[l]);
+  add(8, S.OL, (size_t)LSTM_H * S.V * LSTM_NH); add(8, S.output, (size_t)LSTM_H * LSTM_VP);
+  add(9, S.input_history, LSTM_H); add(9, S.bp_symbol, LSTM_H); add(9, S.dyn, 4);
+  add(10, S.byte_probs, 256); add(10, h->d_prev_probs, 256);
+  add(10, S.raw_ring, (size_t)LSTM_L * LSTM_H * 3 * LSTM_C); add(10, S.h_ring, (size_t)LSTM_H * LSTM_NH); add(10, S.logit_ring, (size_t)LSTM_H * LSTM_VP);
+  add(10, S.bp_pub, (size_t)2 * LSTM_H * 2 * LSTM_C);
+  if (k != LSTM_STATE_ARRAYS) { cmx_set_err("cmx_lstm_state_view: internal layout error"); return 1; }
+  *n = k; *device = h->device;
+  if (counters) { counters[0] = h->bytes_done; counters[1] = (uint64_t)h->hc; counters[2] = h->bptt_rounds; }
+  return 0;
+}
+
 }  // extern "C"

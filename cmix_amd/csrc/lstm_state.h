@@ -125,4 +125,9 @@ size_t lstm_wt_index(int V, int insz, int c, int i) {
 }
 #endif
 
+// one array of a handle's state in HBM, as cmx_lstm_state_diff walks them (lstm_vote.hip); region numbers and array order: include/cmix_amd.h
+#define LSTM_REGIONS 11
+#define LSTM_STATE_ARRAYS 80
+struct LstmRegion { int region; uint32_t* p; unsigned long long words; };
+
 #endif

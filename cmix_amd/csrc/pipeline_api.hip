@@ -141,6 +141,13 @@ struct Slot {
   unsigned long long* h_cxvote = nullptr;              // pinned [12]: the context vote's record as it stood behind this chunk, then the chunk's own result
   hipEvent_t ev_cx[2] = {nullptr, nullptr}, ev_cxvote = nullptr;
   bool cxvoted = false;                                // this slot's chunk has a context vote behind it: slot_done waits for ev_cxvote too
+  // shadow LSTM stages (cmx_pipeline_set_lstm_shadow): allocated at the first begin, nothing of it otherwise
+  float* d_lsout[2] = {nullptr, nullptr};              // [max][256] distributions of shadow i + 1
+  float* d_lsp[2] = {nullptr, nullptr};                // [8 max] its bit predictions (dense)
+  int* d_lsex[2] = {nullptr, nullptr};                 // [8 max] its ex
+  unsigned long long* h_lsvote = nullptr;              // pinned [12]: the LSTM vote's record as it stood behind this chunk, then the chunk's own result; then the shadows' two sticky hand-off flags
+  hipEvent_t ev_ls[2] = {nullptr, nullptr}, ev_lsvote = nullptr;
+  bool lsvoted = false;                                // this slot's chunk has an LSTM vote behind it: slot_done waits for ev_lsvote too
   // stream journal (cmx_pipeline_set_journal): allocated at the set call, nothing of it otherwise
   unsigned long long* d_jr = nullptr;                  // the chunk's partial records on the device
   uint64_t* h_jr = nullptr;                            // pinned: their copy, complete when ev_jr is
@@ -245,6 +252,11 @@ struct cmx_pipeline {
   cmx_ctxmodels_t* cx[2] = {nullptr, nullptr};    // compact handles, created at the first begin (or pretrain)
   cmx_ctxvote_t* cxvote = nullptr;
   uint64_t cxvote_bits = 0;      // stream bits handed to the context vote so far
+  int lstm_shadow = 0;           // cmx_pipeline_set_lstm_shadow: shadow LSTM stages beside h->lstm (0 = off: nothing below exists)
+  hipStream_t s_ls[2] = {nullptr, nullptr};       // their streams (from the factory, at set_lstm_shadow: the queue budget refuses there)
+  cmx_lstm_t* ls[2] = {nullptr, nullptr};         // created at the first begin
+  cmx_lstmvote_t* lsvote = nullptr;
+  uint64_t lsvote_bytes = 0;     // stream bytes handed to the LSTM vote so far
   bool pretrained = false;       // cmx_pipeline_pretrain has run: shadow context stages set after it would start untrained
   float* dbg_mix = nullptr;      // diagnosis (cmx_pipeline_debug_mix_out): the 47 mixer outputs of every bit, [bit][47], as far as dbg_mix_cap bits
   uint64_t dbg_mix_cap = 0, dbg_mix_bits = 0;
@@ -274,11 +286,12 @@ void collect(cmx_pipeline* h, Slot& s) {  // the slot's chunk has finished (its 
 // The overlap probe on every stream of the handle (include/cmix_amd.h, cmx_pipeline_stage_overlap): the stage streams, the upload stream,
 // paq8's role streams and, in a decoder, the byte model's.
 static int probe_streams(cmx_pipeline* h) {
-  hipStream_t q[24] = {h->s_lstm, h->s_ctx, h->s_mix, h->s_up, h->s_fx, h->s_p8, h->late ? h->late->s_bm : nullptr};
+  hipStream_t q[26] = {h->s_lstm, h->s_ctx, h->s_mix, h->s_up, h->s_fx, h->s_p8, h->late ? h->late->s_bm : nullptr};
   int n = 7;
   if (h->p8) n += cmx_p8stage_streams(h->p8, q + n, 24 - n);
   for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_sh[i];   // (null entries are skipped)
   for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_cx[i];
+  for (int i = 0; i < 2 && n < 26; ++i) q[n++] = h->s_ls[i];
   const int all = cmx_overlap_probe(q, n, &h->probe_n);
   h->probe_all = all < 0 ? 0 : all;
   h->overlap = all < 0 ? -1 : all == h->probe_n ? 1 : 0;
@@ -290,6 +303,7 @@ static hipError_t slot_done(Slot& s) {
   hipError_t e = hipEventSynchronize(s.ev_mix1);
   if (e == hipSuccess && s.journalled) e = hipEventSynchronize(s.ev_jr);
   if (e == hipSuccess && s.cxvoted) e = hipEventSynchronize(s.ev_cxvote);
+  if (e == hipSuccess && s.lsvoted) e = hipEventSynchronize(s.ev_lsvote);
   return e == hipSuccess && s.voted ? hipEventSynchronize(s.ev_vote) : e;
 }
 // the journal's partial records of every finished chunk below `upto`, in stream order (each chunk's copy is waited for: they land in order on s_mix)
@@ -319,6 +333,16 @@ static std::string ctx_vote_text(const unsigned long long r[8]) {
   static const int kFirstCol = 2025 - 3;   // lane order: layer-0 columns 0, 1, 2, 2025..2075
   std::string s = "context shadow vote: the " + std::to_string(r[2]) + " context-stage instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream bit " +
                   std::to_string(r[4]) + ", " + (r[5] < 54 ? "layer-0 column " + std::to_string(r[5] < 3 ? r[5] : kFirstCol + r[5]) : "selector " + std::to_string(r[5] - 54)) + ": ";
+  if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
+  else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own stage)" : "");
+  return s + " (the stream's output is void)";
+}
+// What an LSTM vote's record (cmx_lstmvote_report's eight words) says, for an error message
+static std::string lstm_vote_text(const unsigned long long r[8]) {
+  const unsigned long long c = r[5];
+  std::string s = "LSTM shadow vote: the " + std::to_string(r[2]) + " LSTM-stage instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream byte " +
+                  std::to_string(r[4]) + ", " + (c < 256 ? "distribution entry " + std::to_string(c) : c < 264 ? "bit " + std::to_string(c - 256) + "'s prediction (layer-0 column 2077)" :
+                                                 "bit " + std::to_string(c - 264) + "'s ex") + ": ";
   if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
   else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own stage)" : "");
   return s + " (the stream's output is void)";
@@ -436,6 +460,30 @@ static void ctx_shadow_drop(cmx_pipeline* h) {
   h->ctx_shadow = 0;
 }
 
+// everything cmx_pipeline_set_lstm_shadow and the first begin behind it made
+static void lstm_shadow_drop(cmx_pipeline* h) {
+  if (!h->lstm_shadow) return;
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();
+  cmx_lstmvote_destroy(h->lsvote); h->lsvote = nullptr;
+  for (int i = 0; i < 2; ++i) {
+    cmx_lstm_destroy(h->ls[i]); h->ls[i] = nullptr;
+    if (h->s_ls[i]) cmx_destroy_stream(h->s_ls[i]);
+    h->s_ls[i] = nullptr;
+  }
+  for (Slot& s : h->slot) {
+    for (float*& p : s.d_lsout) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float*& p : s.d_lsp) { if (p) (void)hipFree(p); p = nullptr; }
+    for (int*& p : s.d_lsex) { if (p) (void)hipFree(p); p = nullptr; }
+    if (s.h_lsvote) (void)hipHostFree(s.h_lsvote);
+    s.h_lsvote = nullptr;
+    for (hipEvent_t* e : {&s.ev_ls[0], &s.ev_ls[1], &s.ev_lsvote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    s.lsvoted = false;
+  }
+  wg_unclaim(h, 52 * h->lstm_shadow);
+  h->lstm_shadow = 0;
+}
+
 void cmx_pipeline_destroy(cmx_pipeline_t* h) {
   if (!h) return;
   if (h->late) {
@@ -456,6 +504,7 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
   }
   shadow_drop(h);
   ctx_shadow_drop(h);
+  lstm_shadow_drop(h);
   wg_release(h);
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
@@ -630,6 +679,7 @@ int cmx_pipeline_set_tolerance(cmx_pipeline_t* h, int on) {
   if (!h) { cmx_set_err("cmx_pipeline_set_tolerance: null handle"); return 1; }
   if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_tolerance: only before the first chunk"); return 1; }
   if (on && h->shadow) { cmx_set_err("cmx_pipeline_set_tolerance: shadow mixing networks are set (the vote compares strict kernels)"); return 1; }
+  if (on && h->lstm_shadow) { cmx_set_err("cmx_pipeline_set_tolerance: shadow LSTM stages are set (the vote compares strict kernels)"); return 1; }
   // the mixing network first (it can refuse: after the stream's first bit); the LSTM's switch (its weight-update contraction
   // on the matrix cores) follows and is rolled back with the network's if it fails, so that the two never disagree about the mode
   const int was = cmx_mixnet_mode(h->mix);
@@ -782,6 +832,73 @@ int cmx_pipeline_debug_ctx_shadow_xor(cmx_pipeline_t* h, int instance, int regio
   if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_ctx_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
   return cmx_ctxmodels_debug_state_xor(x, region, lane, index, xor_mask);
 }
+// ---- shadow LSTM stages and their vote (include/cmix_amd.h; lstm_vote.hip) ----
+// Reserves here what can be refused -- k streams of the factory (the queue budget) and 52 resident workgroups per shadow --; the k handles, the vote
+// and the per-slot buffers are made at the first begin. Allowed after cmx_pipeline_pretrain: the LSTM is not pretrained.
+int cmx_pipeline_set_lstm_shadow(cmx_pipeline_t* h, int k) {
+  if (!h) { cmx_set_err("cmx_pipeline_set_lstm_shadow: null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err("cmx_pipeline_set_lstm_shadow: k must be 0, 1 or 2 shadow LSTM stages (a vote has 2 or 3 instances)"); return 1; }
+  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_lstm_shadow: only before the first chunk"); return 1; }
+  if (k && (h->lstm_tolerance || cmx_mixnet_mode(h->mix) == 1)) { cmx_set_err("cmx_pipeline_set_lstm_shadow: the tolerance switch is set (the vote compares strict kernels)"); return 1; }
+  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  if (k == h->lstm_shadow) return 0;
+  lstm_shadow_drop(h);
+  if (k == 0) return probe_streams(h) < 0 ? 1 : 0;
+  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) {
+    cmx_set_err("cmx_pipeline_set_lstm_shadow: this process holds " + std::to_string(cmx_hw_queues(h->device)) + " dedicated hardware queues on device " + std::to_string(h->device) +
+                " and " + std::to_string(k) + " shadow LSTM stage(s) need one each, the limit is " + std::to_string(CMX_MAX_HW_QUEUES));
+    return 1;
+  }
+  if (!wg_claim(h, 52 * k, "cmx_pipeline_set_lstm_shadow")) return 1;
+  h->lstm_shadow = k;
+  for (int i = 0; i < k; ++i)
+    if (cmx_make_stream(&h->s_ls[i], 0)) { lstm_shadow_drop(h); return 1; }   // (the factory has said why)
+  return probe_streams(h) < 0 ? 1 : 0;
+}
+// the first begin with shadow LSTM stages: the handles, the vote, the per-slot buffers
+static int lstm_shadow_build(cmx_pipeline* h) {
+  const size_t n = h->max_chunk;
+  h->lsvote = cmx_lstmvote_create(h->device, 1 + h->lstm_shadow);
+  if (!h->lsvote) return 1;
+  for (int i = 0; i < h->lstm_shadow; ++i) {
+    h->ls[i] = cmx_lstm_create(h->vocab, 31, h->device);   // as the stream's own (cmx_pipeline_create)
+    if (!h->ls[i]) return 1;
+  }
+  bool ok = hipSetDevice(h->device) == hipSuccess;
+  for (Slot& s : h->slot) {
+    for (int i = 0; i < h->lstm_shadow; ++i)
+      ok = ok && hipMalloc((void**)&s.d_lsout[i], n * 256 * 4) == hipSuccess && hipMalloc((void**)&s.d_lsp[i], 8 * n * 4) == hipSuccess &&
+           hipMalloc((void**)&s.d_lsex[i], 8 * n * 4) == hipSuccess && hipEventCreateWithFlags(&s.ev_ls[i], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&s.h_lsvote, 14 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_lsvote, hipEventDisableTiming) == hipSuccess;
+    if (ok) memset(s.h_lsvote, 0, 14 * 8);
+  }
+  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_begin: buffer allocation for the shadow LSTM stages failed"); return 1; }
+  return 0;
+}
+int cmx_pipeline_lstm_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_pipeline_lstm_shadow_report: bad argument"); return 1; }
+  if (!h->lsvote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
+  return cmx_lstmvote_report(h->lsvote, out);
+}
+int cmx_pipeline_lstm_shadow_values(cmx_pipeline_t* h, uint32_t words[3 * CMX_LSTMVOTE_COLS], uint32_t* byte) {
+  if (!h || !words) { cmx_set_err("cmx_pipeline_lstm_shadow_values: bad argument"); return 1; }
+  if (!h->lsvote) { memset(words, 0, 3 * CMX_LSTMVOTE_COLS * 4); if (byte) *byte = 0; return 0; }
+  return cmx_lstmvote_values(h->lsvote, words, byte);
+}
+static cmx_lstm_t* lstm_shadow_instance(cmx_pipeline* h, int i) { return i == 0 ? h->lstm : i > 0 && i <= h->lstm_shadow ? h->ls[i - 1] : nullptr; }
+int cmx_pipeline_lstm_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[16]) {
+  if (!h || !out) { cmx_set_err("cmx_pipeline_lstm_shadow_state_diff: bad argument"); return 1; }
+  cmx_lstm_t *x = lstm_shadow_instance(h, a), *y = lstm_shadow_instance(h, b);
+  if (!x || !y) { cmx_set_err("cmx_pipeline_lstm_shadow_state_diff: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
+  return cmx_lstm_state_diff(x, y, out);
+}
+int cmx_pipeline_debug_lstm_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t index, uint32_t xor_mask) {
+  if (!h) { cmx_set_err("cmx_pipeline_debug_lstm_shadow_xor: null handle"); return 1; }
+  cmx_lstm_t* x = lstm_shadow_instance(h, instance);
+  if (!x) { cmx_set_err("cmx_pipeline_debug_lstm_shadow_xor: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
+  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_lstm_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
+  return cmx_lstm_debug_state_xor(x, region, index, xor_mask);
+}
 // 0 strict, 1 tolerance: not strict as soon as EITHER the mixing network or the LSTM computes in its tolerance form
 int cmx_pipeline_stage_overlap(cmx_pipeline_t* h) { return h ? h->overlap : -1; }
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t* h) { return !h ? -1 : (h->lstm_tolerance ? 1 : cmx_mixnet_mode(h->mix)); }
@@ -879,6 +996,31 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
   // the stage's sticky time-out flag, in stream order behind its kernels: cmx_pipeline_wait looks at it per chunk
   (void)hipMemcpyAsync(&s.h_fail[0], cmx_lstm_fail_flag(h->lstm), 4, hipMemcpyDeviceToHost, h->s_lstm);
   (void)hipEventRecord(s.ev_lstm1, h->s_lstm);
+  if (h->lstm_shadow) {   // ---- the same bytes and PPMd distributions (both behind ev_in) on every shadow LSTM stage, into buffers of its own; then the vote on the last shadow's stream ----
+    if (!h->lsvote && lstm_shadow_build(h)) return 1;   // (nothing downstream of the stream's own stage waits for any of this)
+    const int k = h->lstm_shadow;
+    int* const ex0 = (int*)(s.d_hint + (8 * h->max_chunk + 1));
+    const float* vd[3] = {s.d_lstm_out, nullptr, nullptr};
+    const float* vp[3] = {d_layer0 + 2077, nullptr, nullptr};
+    const int* vx[3] = {ex0, nullptr, nullptr};
+    const size_t stride[3] = {CMX_N_INPUTS, 1, 1};
+    for (int i = 0; i < k; ++i) {
+      hipStream_t q = h->s_ls[i];
+      (void)hipStreamWaitEvent(q, s.ev_in, 0);
+      if (cmx_lstm_run(h->ls[i], s.d_ppmd + 256, s.d_bytes, n, s.d_lsout[i], s.d_lsp[i], 1, s.d_lsex[i], q)) return 1;
+      (void)hipMemcpyAsync((unsigned*)(s.h_lsvote + 12) + i, cmx_lstm_fail_flag(h->ls[i]), 4, hipMemcpyDeviceToHost, q);
+      (void)hipEventRecord(s.ev_ls[i], q);
+      vd[i + 1] = s.d_lsout[i]; vp[i + 1] = s.d_lsp[i]; vx[i + 1] = s.d_lsex[i];
+    }
+    hipStream_t q = h->s_ls[k - 1];
+    (void)hipStreamWaitEvent(q, s.ev_lstm1, 0);
+    for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_ls[i], 0);
+    if (cmx_lstmvote_run(h->lsvote, vd, vp, stride, vx, n, h->lsvote_bytes, s.d_bytes, q)) return 1;
+    (void)hipMemcpyAsync(s.h_lsvote, cmx_lstmvote_record(h->lsvote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
+    (void)hipEventRecord(s.ev_lsvote, q);
+    s.lsvoted = true;
+    h->lsvote_bytes += n;
+  }
   lap(2);
   if (h->fxcm) {  // ---- fxcm stage: hints from the LSTM's columns, then the parser (this thread) and the kernel on its own stream ----
     const size_t T = 8 * n;
@@ -1272,6 +1414,20 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
     h->failed = true;
     return 1;
   }
+  if (s.lsvoted) {
+    const unsigned* lsfail = (const unsigned*)(s.h_lsvote + 12);
+    if (lsfail[0] || lsfail[1]) {
+      cmx_set_err("cmx_pipeline_wait: an in-launch hand-off of the LSTM kernels of shadow instance " + std::to_string(lsfail[0] ? 1 : 2) +
+                  " timed out (workgroups not co-resident?): the LSTM vote is void from chunk " + std::to_string(index) + " on");
+      h->failed = true;
+      return 1;
+    }
+    if (s.h_lsvote[3]) {   // the LSTM-stage instances disagreed in this chunk or an earlier one (the record is sticky): no repair, the stream stops
+      cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + lstm_vote_text(s.h_lsvote));
+      h->failed = true;
+      return 1;
+    }
+  }
   if (s.cxvoted && s.h_cxvote[3]) {   // the context-stage instances disagreed in this chunk or an earlier one (the record is sticky): no repair, the stream stops
     cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + ctx_vote_text(s.h_cxvote));
     h->failed = true;
@@ -1321,6 +1477,7 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
   if (h->p8) ok = cmx_p8stage_sync(h->p8) == 0 && ok;
   for (hipStream_t q : h->s_sh) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   for (hipStream_t q : h->s_cx) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
+  for (hipStream_t q : h->s_ls) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (!ok) { cmx_set_err("cmx_pipeline_sync: device error"); h->failed = true; return 1; }
   if (cmx_ctxmodels_sync(h->ctx) || cmx_mixnet_sync(h->mix)) { h->failed = true; return 1; }
   for (cmx_ctxmodels_t* c : h->cx) if (c && cmx_ctxmodels_sync(c)) { h->failed = true; return 1; }
@@ -1328,6 +1485,16 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
     uint64_t r[8];
     if (cmx_ctxvote_report(h->cxvote, r)) { h->failed = true; return 1; }
     if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + ctx_vote_text(t)); h->failed = true; return 1; }
+  }
+  for (int i = 0; i < 2; ++i)
+    if (h->ls[i] && cmx_lstm_failed(h->ls[i])) {
+      cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the LSTM kernels of shadow instance " + std::to_string(i + 1) + " timed out (workgroups not co-resident?): the LSTM vote is void");
+      h->failed = true; return 1;
+    }
+  if (h->lsvote) {
+    uint64_t r[8];
+    if (cmx_lstmvote_report(h->lsvote, r)) { h->failed = true; return 1; }
+    if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + lstm_vote_text(t)); h->failed = true; return 1; }
   }
   for (cmx_mixnet_t* m : h->sh) if (m && cmx_mixnet_sync(m)) { h->failed = true; return 1; }
   if (h->vote) {
@@ -1433,6 +1600,7 @@ int cmx_pipeline_late_start(cmx_pipeline_t* h, int last_bit) {
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   if (hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_pipeline_late_start: device error"); return 1; }   // pretraining is complete
   ctx_shadow_drop(h);
+  lstm_shadow_drop(h);
   shadow_drop(h);   // a decoder is not covered by the vote (include/cmix_amd.h): it holds no stream, workgroup or buffer of it
   Late* L = new Late();
   h->late = L;

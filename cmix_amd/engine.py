@@ -209,6 +209,25 @@ def lib():
         L.cmx_pipeline_ctx_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_pipeline_ctx_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.cmx_pipeline_debug_ctx_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]
+        L.cmx_lstmvote_create.restype = C.c_void_p
+        L.cmx_lstmvote_create.argtypes = [C.c_int, C.c_int]
+        L.cmx_lstmvote_destroy.argtypes = [C.c_void_p]
+        L.cmx_lstmvote_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.cmx_lstmvote_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_lstmvote_record.restype = C.c_void_p
+        L.cmx_lstmvote_record.argtypes = [C.c_void_p]
+        L.cmx_lstmvote_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_lstmvote_last.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_lstm_state_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_lstm_debug_state_xor.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32]
+        L.cmx_lstm_debug_layout.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_set_lstm_shadow.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_pipeline_lstm_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_lstm_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_lstm_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.cmx_pipeline_debug_lstm_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32]
+        L.cmx_set_lstm_shadow.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_lstm_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_set_ctx_shadow.argtypes = [C.c_void_p, C.c_int]
         L.cmx_ctx_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_debug_ctx_shadow_xor.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]
@@ -463,6 +482,108 @@ class CtxVote:
     def close(self):
         if getattr(self, "h", None):
             lib().cmx_ctxvote_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# the redundant LSTM-stage vote (include/cmix_amd.h, cmx_lstmvote_*; the rule's specification is cmix_amd.lstmvote.lstm_vote_reference)
+LSTM_STATE_REGIONS = ("W", "WT", "M", "Vv", "gb", "caches", "recurrent", "layer_input", "output_layer", "indices", "probs_rings")
+LSTMVOTE_COLS = 272   # CMX_LSTMVOTE_COLS: the 256 distribution words of a byte, its 8 bit predictions, its 8 ex words
+# the arrays of cmx_lstm_state_diff in their fixed order (l = layer outside, g = gate inside)
+LSTM_STATE_ARRAYS = tuple(["%s[%d][%d]" % (a, l, g) for a in ("W", "WT", "M", "Vv", "gb") for l in range(2) for g in range(3)] + ["adam_tab"] +
+                          ["%s[%d][%d]" % (a, l, g) for a in ("norm", "gstate", "ivar", "E") for l in range(2) for g in range(3)] +
+                          ["%s[%d]" % (a, l) for a in ("last_state", "tanh_state", "in_gate_state") for l in range(2)] +
+                          ["stateb[0][0]", "stateb[0][1]", "stateb[1][0]", "stateb[1][1]", "hid[0]", "hid[1]", "layer_input[0]", "layer_input[1]", "OL", "output",
+                           "input_history", "bp_symbol", "dyn", "byte_probs", "d_prev_probs", "raw_ring", "h_ring", "logit_ring", "bp_pub"])
+
+
+def _lstm_region(r):
+    return LSTM_STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
+
+
+def _lstm_vote_values(fn, h, n):
+    words, byte = np.zeros(3 * LSTMVOTE_COLS, np.uint32), C.c_uint32(0)
+    if fn(h, words.ctypes.data, C.byref(byte)):
+        raise CmxError(last_error())
+    return {"words": words[:LSTMVOTE_COLS * n].reshape(n, LSTMVOTE_COLS).copy(), "byte": int(byte.value)}
+
+
+def _lstm_state_diff(out):
+    v = [int(x) for x in out]
+    first = {"region": v[1], "index": v[2], "a": v[3], "b": v[4]} if v[0] else None
+    return {"words": v[0], "first": first, "per_region": dict(zip(LSTM_STATE_REGIONS, v[5:16])), "raw": v}
+
+
+def lstm_layout(lstm):
+    """the state arrays of an Lstm handle in cmx_lstm_state_diff's order (cmx_lstm_debug_layout): list of dicts name, region (its name), offset (words
+    inside the region), words -- for the handle's vocabulary size"""
+    out = (C.c_uint64 * (3 * len(LSTM_STATE_ARRAYS)))()
+    n = lib().cmx_lstm_debug_layout(lstm.h, out)
+    if n != len(LSTM_STATE_ARRAYS):
+        raise CmxError(last_error() if n < 0 else "cmx_lstm_debug_layout: %d arrays, expected %d" % (n, len(LSTM_STATE_ARRAYS)))
+    return [{"name": LSTM_STATE_ARRAYS[i], "region": LSTM_STATE_REGIONS[int(out[3 * i])], "offset": int(out[3 * i + 1]), "words": int(out[3 * i + 2])} for i in range(n)]
+
+
+class LstmVote:
+    """The LSTM-stage vote kernel over n = 2 or 3 instances' distributions [N, 256], bit predictions and ex [N, 8] (CUDA tensors of 4-byte words); an
+    instance's bit predictions may instead be a [8N, 2078] layer-0 matrix, read in place from its column 2077. The record is sticky across run()."""
+
+    def __init__(self, n, device=0):
+        self.n = int(n)
+        self.h = lib().cmx_lstmvote_create(device, self.n)
+        if not self.h:
+            raise CmxError(last_error())
+
+    def run(self, dists, bit_ps, exs, stream_byte0=0, data=None, stream=None):
+        import torch
+        assert len(dists) == self.n and len(bit_ps) == self.n and len(exs) == self.n
+        N = int(exs[0].numel()) // 8
+        ptr, stride = [], []
+        for d, p, x in zip(dists, bit_ps, exs):
+            assert d.is_cuda and p.is_cuda and x.is_cuda and d.is_contiguous() and p.is_contiguous() and x.is_contiguous()
+            assert d.element_size() == 4 and p.element_size() == 4 and x.element_size() == 4 and d.numel() == N * 256 and x.numel() == N * 8
+            if p.dim() == 2 and p.shape == (8 * N, N_INPUTS):   # layer-0 rows: column 2077 in place
+                ptr.append(p.data_ptr() + 4 * (N_INPUTS - 1))
+                stride.append(N_INPUTS)
+            else:
+                assert p.numel() == N * 8
+                ptr.append(p.data_ptr())
+                stride.append(1)
+        if stream is None:
+            stream = torch.cuda.current_stream(dists[0].device).cuda_stream
+        ad = (C.c_void_p * 3)(*[d.data_ptr() for d in dists])
+        ap = (C.c_void_p * 3)(*ptr)
+        ast = (C.c_size_t * 3)(*stride)
+        ax = (C.c_void_p * 3)(*[x.data_ptr() for x in exs])
+        if lib().cmx_lstmvote_run(self.h, ad, ap, ast, ax, N, int(stream_byte0), data.data_ptr() if data is not None else None, C.c_void_p(stream)):
+            raise CmxError(last_error())
+
+    def report(self):
+        """as Vote.report with bytes for bits: bits = bytes voted, first_bit = the first event's stream byte, column = the element's c (0..255
+        distribution entry, 256..263 bit prediction, 264..271 ex). Synchronises the device."""
+        return _vote_report(lib().cmx_lstmvote_report, self.h)
+
+    def last(self):
+        """as Vote.last (bit = the stream byte)"""
+        out = (C.c_uint64 * 4)()
+        if lib().cmx_lstmvote_last(self.h, out):
+            raise CmxError(last_error())
+        v = [int(x) for x in out]
+        ev = v[0] != 0
+        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
+
+    def values(self):
+        """the captured row of the first event: words [n, 272] u32, byte"""
+        return _lstm_vote_values(lib().cmx_lstmvote_values, self.h, self.n)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().cmx_lstmvote_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -765,6 +886,19 @@ class Lstm:
         if rc:
             raise CmxError(last_error())
         return out, bp, bx
+
+    def state_diff(self, other):
+        """Every word of this handle's and `other`'s state in HBM compared (include/cmix_amd.h, cmx_lstm_state_diff): dict words, first (region, index,
+        a, b), per_region, raw. Raises when a host-side counter differs. Synchronises the device."""
+        out = (C.c_uint64 * 16)()
+        if lib().cmx_lstm_state_diff(self.h, other.h, out):
+            raise CmxError(last_error())
+        return _lstm_state_diff(out)
+
+    def debug_state_xor(self, region, index, xor_mask):
+        """Test hook: XOR one state word (region: number or LSTM_STATE_REGIONS name) between runs; the index region is refused."""
+        if lib().cmx_lstm_debug_state_xor(self.h, _lstm_region(region), int(index), int(xor_mask)):
+            raise CmxError(last_error())
 
     def gate_weights(self, layer, gate):
         n = lib().cmx_lstm_gate_rowlen(self.h, layer)
@@ -1105,6 +1239,33 @@ class Pipeline:
         if lib().cmx_pipeline_debug_ctx_shadow_xor(self.h, int(instance), _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
+    def set_lstm_shadow(self, k):
+        """k = 0 / 1 / 2 shadow LSTM stages voting on every chunk's distributions, bit predictions and ex (include/cmix_amd.h): before the first
+        chunk (pretrain may have run: the LSTM is not pretrained); wait / fetch / sync then fail the chunk in which the instances disagree."""
+        if lib().cmx_pipeline_set_lstm_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+        self._lstm_shadow = int(k)
+
+    def lstm_shadow_report(self):
+        """as LstmVote.report (all zero while nothing was voted)"""
+        return _vote_report(lib().cmx_pipeline_lstm_shadow_report, self.h)
+
+    def lstm_shadow_values(self):
+        """as LstmVote.values"""
+        return _lstm_vote_values(lib().cmx_pipeline_lstm_shadow_values, self.h, 1 + getattr(self, "_lstm_shadow", 0))
+
+    def lstm_shadow_state_diff(self, a, b):
+        """Lstm.state_diff of instances a and b (0 = the stream's own stage, 1.. = the shadows)"""
+        out = (C.c_uint64 * 16)()
+        if lib().cmx_pipeline_lstm_shadow_state_diff(self.h, int(a), int(b), out):
+            raise CmxError(last_error())
+        return _lstm_state_diff(out)
+
+    def debug_lstm_shadow_xor(self, instance, region, index, xor_mask):
+        """Test hook: Lstm.debug_state_xor on one instance, between chunks."""
+        if lib().cmx_pipeline_debug_lstm_shadow_xor(self.h, int(instance), _lstm_region(region), int(index), int(xor_mask)):
+            raise CmxError(last_error())
+
     def mixnet_mode(self):
         """0 strict (bit-exact, the default), 1 tolerance -- as the library reports it"""
         return lib().cmx_pipeline_mixnet_mode(self.h)
@@ -1385,6 +1546,15 @@ class Predictor:
     def ctx_shadow_report(self):
         """as CtxVote.report (all zero unless the handle compresses)"""
         return _vote_report(lib().cmx_ctx_shadow_report, self.h)
+
+    def set_lstm_shadow(self, k):
+        """Shadow LSTM stages of the look-ahead pipeline (include/cmix_amd.h, cmx_set_lstm_shadow): before the first stage_input / Predict."""
+        if lib().cmx_set_lstm_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+
+    def lstm_shadow_report(self):
+        """as LstmVote.report (all zero unless the handle compresses)"""
+        return _vote_report(lib().cmx_lstm_shadow_report, self.h)
 
     def debug_ctx_shadow_xor(self, after_chunk, instance, region, lane, index, xor_mask):
         """Test hook: one Pipeline.debug_ctx_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""

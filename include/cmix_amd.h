@@ -126,6 +126,12 @@ int cmx_debug_shadow_xor(cmx_t*, uint64_t after_chunk, int instance, int region,
 int cmx_set_ctx_shadow(cmx_t*, int k);
 int cmx_ctx_shadow_report(cmx_t*, uint64_t out[8]);
 int cmx_debug_ctx_shadow_xor(cmx_t*, uint64_t after_chunk, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask);
+/* Shadow LSTM stages of the look-ahead pipeline (cmx_pipeline_set_lstm_shadow, k = 0 / 1 / 2): before the first cmx_stage_input or cmx_predict.
+ * cmx_predict then returns < 0 instead of a probability of a chunk in which the LSTM instances disagreed. A handle that decodes is not covered. The
+ * programs in integration/ read CMIX_LSTM_SHADOW=1|2; the library reads no environment variable for it. cmx_lstm_shadow_report: as
+ * cmx_lstmvote_report. */
+int cmx_set_lstm_shadow(cmx_t*, int k);
+int cmx_lstm_shadow_report(cmx_t*, uint64_t out[8]);
 /* The stream journal of a cmx_t (section "Stream journal" below has the digest; log2_block_bits 0 = off, else 6..19, 19 = the reference trace's 64 KB;
  * before the first cmx_stage_input / cmx_predict). A COMPRESSOR's handle (look-ahead mode) journals every chunk on the device
  * (cmx_pipeline_set_journal: all 179 words per block; coexists with verify, the shadows and repair). A DECODER's handle (late-bit mode)
@@ -346,6 +352,65 @@ int cmx_lstm_set_tolerance(cmx_lstm_t*, int on);
  * kernels to learn of a timed-out hand-off without synchronising the device. */
 const unsigned* cmx_lstm_fail_flag(cmx_lstm_t*);
 int cmx_glibc_rand_selftest(uint32_t seed, int n, int* out);
+/* THE REDUNDANT LSTM-STAGE VOTE (opt-in; src/lstm_vote.hip). This stage writes layer-0 column 2077 and, through lstmpr / lstmex, steers fxcm's mixer
+ * selection and APMs; its state learns online, and its block kernels hand values between 52 workgroups inside a launch. Verify mode, the network's vote
+ * and the context vote take its column as given. The complementary guard runs the unchanged cmx_lstm_run on n = 2 or 3 handles over the same bytes and
+ * the same PPMd distributions and compares what they wrote. A chunk of nbytes has nbytes rows; per row (byte b) and instance 272 values are compared as
+ * 32-bit WORDS, never as floats (-0.0 differs from 0.0, equal NaN patterns are equal). Elements are ordered by e = b * 272 + c: c = 0..255 the
+ * distribution after byte b (d_out_probs[b][c]; entries outside the vocabulary are written as 0 and compared too), c = 256..263 the ByteModel::Predict
+ * value of the byte's bit c - 256 (layer-0 column 2077 of row 8 b + c - 256), c = 264..271 `ex` of the byte's bit c - 264. The rule is cmx_vote_run's:
+ * n = 3: all equal agree, exactly two equal make the third the ODD instance, all different is NO MAJORITY; n = 2: different is no majority.
+ * cmx_lstmvote_run is asynchronous on `stream`: per instance i the DEVICE arrays d_dist[i] [nbytes][256], d_bit_p[i] with bit k of byte b at
+ * [(8 b + k) * pstride[i]] (pstride 1 = a dense [nbytes][8] array; 2078 with d_bit_p = layer0 + 2077 = read in place from the slot's layer-0 rows:
+ * instance 0 is the stream's own stage) and d_bit_ex[i] [nbytes][8]. 4-byte loads only: nothing is assumed about alignment. d_bytes ([nbytes], may be
+ * NULL: captured as 0) are the chunk's bytes. One kernel with one wavefront per row (grid-stride) and a one-wave kernel behind it that folds the chunk
+ * into the sticky DEVICE record.
+ * _report / _record / _last: exactly the eight / four words of cmx_vote_report / _record / _last with BYTES where those have bits: [1] bytes voted,
+ * [4] (of _last: [1]) the stream byte of the first event, [5] (of _last: [2]) the element's c; "first" = lowest byte, then lowest element.
+ * cmx_lstmvote_values: the capture of the first event's row -- words[i * 272 + c] of instance i (n x 272 used) and the byte coded. Synchronises.
+ * NO REPAIR: by the time the host sees a vote, fxcm and the final network have consumed what the LSTM wrote on the device; correcting it would mean
+ * running those stages again. An event stops the stream. Out of scope as well: the slot's other producers (fxcm, paq8, PPMd), PPMd's distributions
+ * and the bytes (every instance reads the same), the decoder's form of the stage. */
+#define CMX_LSTMVOTE_COLS 272
+typedef struct cmx_lstmvote cmx_lstmvote_t;
+cmx_lstmvote_t* cmx_lstmvote_create(int device, int n);
+void cmx_lstmvote_destroy(cmx_lstmvote_t*);
+int cmx_lstmvote_run(cmx_lstmvote_t*, const float* const* d_dist, const float* const* d_bit_p, const size_t* pstride, const int* const* d_bit_ex, size_t nbytes,
+                     uint64_t stream_byte0, const uint8_t* d_bytes, void* stream);
+int cmx_lstmvote_report(cmx_lstmvote_t*, uint64_t out[8]);
+const unsigned long long* cmx_lstmvote_record(cmx_lstmvote_t*);
+int cmx_lstmvote_values(cmx_lstmvote_t*, uint32_t words[3 * CMX_LSTMVOTE_COLS], uint32_t* byte);
+int cmx_lstmvote_last(cmx_lstmvote_t*, uint64_t out[4]);
+/* Every 32-bit word of two handles' state in HBM, compared (both on one device, same vocabulary size; a == b is refused; synchronises; tens of MB per
+ * handle: after an event and in tests, between chunks only). Regions and, inside a region, the arrays in this order (l = layer 0, 1 outside, g = gate
+ * 0 forget, 1 input node, 2 output inside; an index is a word offset into the region's arrays laid end to end):
+ *   0 W           W[l][g]           [200][rowlen_l]
+ *   1 WT          WT[l][g]          the transposed copies (their tail layout depends on insz_l % 4)
+ *   2 M           M[l][g]           Adam's first moments
+ *   3 Vv          Vv[l][g]          Adam's second moments
+ *   4 gb          gb[l][g]          [8][200]: gamma, beta and their moments and updates (index 0 = gamma of layer 0's forget gate, cell 0); then adam_tab
+ *   5 caches      norm[l][g], gstate[l][g], ivar[l][g], E[l][g], then last_state[l], tanh_state[l], in_gate_state[l]: the per-step caches of the horizon
+ *   6 recurrent   stateb[0][l] (= state[l]), stateb[1][l], hid[0], hid[1]
+ *   7 layer_input layer_input[l]    [100][insz_l]
+ *   8 output_layer OL [100][V][401], output [100][256]
+ *   9 indices     input_history [100], bp_symbol [100], dyn [4]
+ *  10 probs_rings byte_probs [256], the handle's d_prev_probs [256], then the in-launch rings raw_ring, h_ring, logit_ring, bp_pub
+ * NOT compared: `sync` (hand-off counters, zeroed ahead of every launch), `blk` (device addresses), `raw` and `logits` (allocated, but no kernel has
+ * read or written them since the block kernels replaced the per-byte ones), `OLT` (null). Every other array -- the rings included: each entry has one
+ * writer and a fixed summation order -- is a function of the bytes, PPMd's distributions and the chunk boundaries alone; no array was found whose
+ * content depends on timing or placement. The host-side counters bytes_done, hc and bptt_rounds are compared first: a difference there is an ERROR
+ * return whose message names the counter. out[0] differing words; [1..4] the first difference in region-then-array-then-address order: region, index,
+ * the word of a, the word of b (UINT64_MAX without a difference); [5..15] the count per region. */
+#define CMX_LSTM_STATE_REGIONS 11
+#define CMX_LSTM_STATE_ARRAYS 80
+int cmx_lstm_state_diff(cmx_lstm_t* a, cmx_lstm_t* b, uint64_t out[16]);
+/* TEST HOOK: XOR one state word (addressed as cmx_lstm_state_diff reports it) between runs. Synchronises the device. REFUSES region 9: its words are
+ * indices and counters the kernels address memory with; everywhere else a changed word is a float the kernels use as a value, never as an address. A
+ * data change only: no kernel stops and no wait times out. */
+int cmx_lstm_debug_state_xor(cmx_lstm_t*, int region, uint64_t index, uint32_t xor_mask);
+/* TEST READOUT: per array, in the order above, [3 i] its region, [3 i + 1] its word offset inside the region, [3 i + 2] its words, for the handle's
+ * vocabulary size; returns the number of arrays (CMX_LSTM_STATE_ARRAYS) or -1. */
+int cmx_lstm_debug_layout(cmx_lstm_t*, uint64_t out[3 * CMX_LSTM_STATE_ARRAYS]);
 
 /* ------------------------------------------------------------------------
  * 2c. Stage: context plumbing + the 54 small native models = ContextManager, the 54 byte / 8 bit
@@ -676,6 +741,29 @@ int cmx_pipeline_ctx_shadow_report(cmx_pipeline_t*, uint64_t out[8]);
 int cmx_pipeline_ctx_shadow_values(cmx_pipeline_t*, uint32_t words[3 * CMX_CTXVOTE_COLS], uint32_t* bit);
 int cmx_pipeline_ctx_shadow_state_diff(cmx_pipeline_t*, int a, int b, uint64_t out[16]);
 int cmx_pipeline_debug_ctx_shadow_xor(cmx_pipeline_t*, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask);
+/* SHADOW LSTM STAGES (opt-in, k = 0 off / 1 / 2; strict mode only; before the first chunk -- and, unlike the shadow context stages, also AFTER
+ * cmx_pipeline_pretrain: the LSTM is not pretrained, predictor.cpp:471-487, so a shadow misses nothing): k cmx_lstm_t made as the stream's own
+ * (cmx_lstm_create(vocab, 31, device), same avoid_xcd setting and environment) run every chunk again on the slot's bytes and PPMd distributions, each
+ * on a stream of its own (also in the reduced-stream modes of CMX_PIPELINE_STREAMS), behind the upload event that covers both, into buffers of their
+ * own ([max][256] distributions, [8 max] bit predictions, [8 max] ex per slot and shadow), and a vote (cmx_lstmvote_*; instance 0 = the stream's own
+ * stage, its bit predictions read in place from column 2077 of the slot's layer-0 rows) follows every chunk on the last shadow's stream. Nothing
+ * downstream of the stream's own LSTM -- fxcm's hints, the final network -- waits for a shadow or for the vote; a slot is not reused before its vote
+ * has read it. Reserved at the set call, refused with the reason: k streams of the queue budget (CMX_MAX_HW_QUEUES) and 52 resident workgroups per
+ * shadow; refused together with the tolerance switch, and cmx_pipeline_set_tolerance is refused while shadows are set. The handles, the vote and the
+ * per-slot buffers are created at the first cmx_pipeline_begin; k = 0 gives everything back, and with k = 0 nothing is allocated, launched or waited
+ * for. cmx_pipeline_wait / _fetch / _sync fail the chunk in which the instances first disagreed -- the message names the chunk, the stream byte,
+ * "distribution entry v", "bit k's prediction (layer-0 column 2077)" or "bit k's ex", and the odd instance or "no majority between 2 instances" -- and
+ * void the handle, which can still be diagnosed (_lstm_shadow_report / _values: as cmx_lstmvote_report / _values, all zero while nothing was voted;
+ * _lstm_shadow_state_diff: cmx_lstm_state_diff of instances a and b, 0 = the stream's own stage) and destroyed. A shadow's sticky time-out flag is
+ * copied back in stream order and names that instance in the "in-launch hand-off of the LSTM" message. NO REPAIR: when the host sees a vote, fxcm and
+ * the network have already consumed what the LSTM wrote on the device; an event stops the stream. Coexists with _set_verify, _set_shadow,
+ * _set_shadow_repair, _set_ctx_shadow and _set_journal. A handle that decodes (cmx_pipeline_late_start) drops the shadows: a decoder is not covered.
+ * _debug_lstm_shadow_xor: the test hook cmx_lstm_debug_state_xor on one instance, between chunks. */
+int cmx_pipeline_set_lstm_shadow(cmx_pipeline_t*, int k);
+int cmx_pipeline_lstm_shadow_report(cmx_pipeline_t*, uint64_t out[8]);
+int cmx_pipeline_lstm_shadow_values(cmx_pipeline_t*, uint32_t words[3 * CMX_LSTMVOTE_COLS], uint32_t* byte);
+int cmx_pipeline_lstm_shadow_state_diff(cmx_pipeline_t*, int a, int b, uint64_t out[16]);
+int cmx_pipeline_debug_lstm_shadow_xor(cmx_pipeline_t*, int instance, int region, uint64_t index, uint32_t xor_mask);
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t*);
 /* STREAM JOURNAL (opt-in; log2_block_bits = 0 off, the default: nothing is allocated, launched or waited for; else 6..19, 19 = the 64 KB block
  * of oracle/ref_long_trace.cpp; before the first chunk). Behind every chunk's mixing network, on the same stream, cmx_journal's kernel digests what

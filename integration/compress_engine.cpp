@@ -147,6 +147,9 @@ int main(int argc, char* argv[]) {
     // CMIX_CTX_SHADOW=1|2: that many shadow context stages vote on every chunk's 54 columns and 47 selectors; a disagreement stops the program
     const char* csh = getenv("CMIX_CTX_SHADOW");
     if (csh && (csh[0] == '1' || csh[0] == '2') && cmx_pipeline_set_ctx_shadow(p.pipe(), csh[0] - '0')) Predictor::Die();
+    // CMIX_LSTM_SHADOW=1|2: that many shadow LSTM stages vote on every chunk's distributions, bit predictions and ex; a disagreement stops the program
+    const char* lsh = getenv("CMIX_LSTM_SHADOW");
+    if (lsh && (lsh[0] == '1' || lsh[0] == '2') && cmx_pipeline_set_lstm_shadow(p.pipe(), lsh[0] - '0')) Predictor::Die();
     // CMIX_JOURNAL=path [CMIX_JOURNAL_LOG2=k, default 19 = 64 KB]: per-block digests of what the mixing network read and wrote, to `path` and `path.inputs` as the run goes
     const char* jr = getenv("CMIX_JOURNAL");
     const char* jl = getenv("CMIX_JOURNAL_LOG2");
