@@ -352,7 +352,9 @@ struct FxXfer {
   unsigned m_done, u_done;          // rows published by role U (m_done: unused since role M publishes per wavefront)
   unsigned pad2;
   unsigned mw_done[FX_M_WAVES];     // rows published by each of role M's wavefronts
+  unsigned jit[FX_M_WAVES + 2];     // NOT zeroed per launch (test hook, fx_jitter_stall): stalls taken by role M's wavefronts, role U, role X since creation
 };
+enum { FX_JIT_U = FX_M_WAVES, FX_JIT_X = FX_M_WAVES + 1 };
 enum { FX_ROW_WORDS = 288,          // one row: 1152 bytes
        FX_ROW_RES = 256,            //   [0, 256) role M: its copy of the 512 inputs (its own range is taken); then the 8 sums
        FX_ROW_UTX = 264,            //   role U: inputs 0..23 as 12 words, word 12 = run map | LSTM input
@@ -403,10 +405,25 @@ __device__ __forceinline__ void fx_stage_ahead(FxAhead* ah, FxLocal* loc, const 
 // LATE (a decoder, cmx_late.h): the chunk's bytes are not known -- bit q arrives through the box LB (with it the host records of
 // the step after it: at a byte's last bit the parser's record of that byte), the LSTM hints of update q through the ByteModel kernel's
 // counter LC_BM2, and role X counts the rows it has completed (LC_FX) for the mixing network. `bytes` is unused; recs is host-mapped.
-template <bool LATE>
+// Test hook (CMX_FXCM_JITTER=seed, tests/test_zgpu_stage_fxcm.py; as jitter_stall of mixnet_chunk.hip): a role stalls at one bit in eight for 0..31 x s_sleep(127)
+// (~100 us at most, three orders of magnitude below FX_ROLE_SPIN's bound). The roles are coupled only through rows followed by a counter, so every result
+// must be independent of how far a role runs ahead of or behind another; on a quiet device M and U run far ahead of X, and "X arrives first and reads the
+// row the moment its counter moves" is the least exercised path. t and site are uniform for the caller (a wavefront of role M, the whole workgroup of role U
+// or X); `leader` (one lane) counts the stall in FxXfer::jit[site].
+template <bool JIT> __device__ __forceinline__ void fx_jitter_stall(FxXfer* X, int jit, int t, int site, bool leader) {
+  if constexpr (!JIT) return;
+  unsigned h = (unsigned)t * 2654435761u + (unsigned)site * 0x9E3779B9u + (unsigned)jit * 0x85EBCA6Bu;
+  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
+  if ((h & 7u) == 0) {
+    const int n = (int)((h >> 3) & 31u);
+    for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
+    if (leader) __hip_atomic_fetch_add(&X->jit[site], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+template <bool LATE, bool JIT = false>
 __device__ __forceinline__ void fx_roles_body(FxDev* gd, FxXfer* X, unsigned* rows, const uint8_t* bytes, const FxByteRec* recs,
                                               const int16_t* lstmpr, const uint8_t* lstmex, float* out, long ostride, int n,
-                                              unsigned long long* prof, CmxLate LB) {
+                                              unsigned long long* prof, CmxLate LB, int jit = 0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fx_smem[];
   __shared__ int late_go;
   FxShared& sh = *(FxShared*)fx_smem;
@@ -495,6 +512,7 @@ __device__ __forceinline__ void fx_roles_body(FxDev* gd, FxXfer* X, unsigned* ro
       uint32_t bv = 0;
       int prev_byte = lastbyte0;
       for (int q = 0; q < nbits; q++) {
+        if constexpr (JIT) fx_jitter_stall<JIT>(X, jit, 2 * q, mw, lane == 0);
         const int b = q >> 3, k = q & 7;
         int cur;
         if (LATE) {   // the byte as far as it is known: the decoded bits on top (only those are used), zeros below
@@ -552,6 +570,7 @@ __device__ __forceinline__ void fx_roles_body(FxDev* gd, FxXfer* X, unsigned* ro
         FX_TICK(4);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wavefront's row stores have reached the coherence point before its counter moves
         __builtin_amdgcn_wave_barrier();
+        if constexpr (JIT) fx_jitter_stall<JIT>(X, jit, 2 * q + 1, mw, lane == 0);
         if (lane == 0) fx_st_u(&X->mw_done[mw], (unsigned)(q + 1));
         FX_TICK(5);
         if (k == 7) prev_byte = cur;
@@ -579,6 +598,7 @@ __device__ __forceinline__ void fx_roles_body(FxDev* gd, FxXfer* X, unsigned* ro
     float* const real_row = q + 1 < nbits ? out + (long)(q + 1) * ostride : gd->pending;
     unsigned* const row = rows + (size_t)q * FX_ROW_WORDS;
     const FxLayout l = u.normal ? ln : fxd_layout(d, 0);
+    if constexpr (JIT) fx_jitter_stall<JIT>(X, jit, q, role == 1 ? FX_JIT_U : FX_JIT_X, tid == 0);   // (q and the site are the same for the whole workgroup)
     if (role == 1) {
       // ================= role U: match models, SSCMs, run map, LSTM input =================
       u.orow = loc.ex[0];
@@ -843,6 +863,13 @@ __global__ __launch_bounds__(FX_DEV_THREADS) void cmx_fxcm_roles_late_kernel(FxD
   fx_roles_body<true>(gd, X, rows, nullptr, recs, lstmpr, lstmex, out, ostride, n, nullptr, box);
 }
 
+// test hook (CMX_FXCM_JITTER, fx_jitter_stall): the compressor's roles with pseudo-random stalls -- an instantiation of its own, so the product kernels carry none of it
+__global__ __launch_bounds__(FX_DEV_THREADS) void cmx_fxcm_roles_jitter_kernel(FxDev* gd, FxXfer* X, unsigned* rows, const uint8_t* bytes, const FxByteRec* recs,
+                                                                                const int16_t* lstmpr, const uint8_t* lstmex, float* out, long ostride, int n,
+                                                                                unsigned long long* prof, int jit) {
+  fx_roles_body<false, true>(gd, X, rows, bytes, recs, lstmpr, lstmex, out, ostride, n, prof, CmxLate(), jit);
+}
+
 __global__ void cmx_fxcm_pattern16_kernel(uint16_t* p, size_t n, const uint16_t* pat, int plen) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = pat[i % (size_t)plen];
 }
@@ -892,6 +919,8 @@ struct cmx_fxcm {
   unsigned* d_rows = nullptr; size_t rows_cap = 0;
   hipStream_t s_up = nullptr; bool own_up = false;   // record uploads: a stream that never has a kernel in front of a copy (cmx_fxcm_set_upload_stream)
   hipEvent_t ev_up[FX_STAGE_BUFS] = {};
+  unsigned ring_waits = 0;   // launches that found their staging slot's previous launch still in flight (cmx_fxcm_debug_ring_waits)
+  int jitter = 0;   // CMX_FXCM_JITTER=1..15 (test hook, tests/test_zgpu_stage_fxcm.py): pseudo-random stalls in every role -- same results, every lead / lag between the roles
   FxByteRec* late_recs[3] = {}; FxByteRec* late_drecs[3] = {}; size_t late_cap[3] = {};   // the decoder's form (cmx_late.h): host-coherent records and their device mirrors (the relay wave copies a byte's record over when the byte is complete), three chunk slots
 };
 
@@ -934,6 +963,8 @@ cmx_fxcm_t* cmx_fxcm_create(const char* dictionary_path, int device) {
   for (int i = 0; ok && i < FX_STAGE_BUFS; i++) ok = hipEventCreateWithFlags(&h->done[i], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&h->ev_up[i], hipEventDisableTiming) == hipSuccess;
   ok = ok && hipFuncSetAttribute((const void*)cmx_fxcm_roles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS_BYTES) == hipSuccess;
   ok = ok && hipFuncSetAttribute((const void*)cmx_fxcm_roles_late_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS_BYTES) == hipSuccess;
+  ok = ok && hipFuncSetAttribute((const void*)cmx_fxcm_roles_jitter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS_BYTES) == hipSuccess;
+  { const char* v = getenv("CMX_FXCM_JITTER"); h->jitter = v ? atoi(v) & 15 : 0; }
   ok = ok && hipMalloc((void**)&h->d_xfer, sizeof(FxXfer)) == hipSuccess && hipMemset(h->d_xfer, 0, sizeof(FxXfer)) == hipSuccess;
   const char* prof = getenv("CMX_FXCM_PROFILE");
   if (ok && prof && prof[0] == '1') ok = hipMalloc((void**)&h->d_prof, 1024) == hipSuccess && hipMemset(h->d_prof, 0, 1024) == hipSuccess;
@@ -951,7 +982,10 @@ int cmx_fxcm_run(cmx_fxcm_t* h, const uint8_t* bytes, const uint8_t* d_bytes, si
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   const int b = h->next;
   h->next = (h->next + 1) % FX_STAGE_BUFS;
-  if (h->used[b] && hipEventSynchronize(h->done[b]) != hipSuccess) { cmx_set_err("cmx_fxcm_run: staging buffer wait failed"); return 1; }
+  if (h->used[b]) {
+    if (hipEventQuery(h->done[b]) == hipErrorNotReady) { h->ring_waits++; (void)hipGetLastError(); }   // (counted for the tests; "not ready" is no error of the stream's)
+    if (hipEventSynchronize(h->done[b]) != hipSuccess) { cmx_set_err("cmx_fxcm_run: staging buffer wait failed"); return 1; }
+  }
   if (h->cap[b] < nbytes) {
     if (h->h_recs[b]) (void)hipHostFree(h->h_recs[b]);
     if (h->d_recs[b]) (void)hipFree(h->d_recs[b]);
@@ -975,9 +1009,14 @@ int cmx_fxcm_run(cmx_fxcm_t* h, const uint8_t* bytes, const uint8_t* d_bytes, si
     if (hipMalloc((void**)&h->d_rows, nbytes * 8 * FX_ROW_WORDS * 4) != hipSuccess) { cmx_set_err("cmx_fxcm_run: row buffer allocation failed"); return 1; }
     h->rows_cap = nbytes;
   }
-  if (hipMemsetAsync((char*)h->d_xfer + 16, 0, sizeof(FxXfer) - 16, s) != hipSuccess) { cmx_set_err("cmx_fxcm_run: hipMemsetAsync failed"); return 1; }
-  hipLaunchKernelGGL(cmx_fxcm_roles_kernel, dim3(FX_M_WGS + 2), dim3(FX_DEV_THREADS), FX_LDS_BYTES, s, h->d_dev, h->d_xfer, h->d_rows, d_bytes, h->d_recs[b], d_lstmpr, d_lstmex,
-                     d_probs + 3, (long)pstride, (int)nbytes, h->d_prof);
+  if (hipMemsetAsync((char*)h->d_xfer + 16, 0, offsetof(FxXfer, jit) - 16, s) != hipSuccess) { cmx_set_err("cmx_fxcm_run: hipMemsetAsync failed"); return 1; }
+  if (h->jitter) {
+    hipLaunchKernelGGL(cmx_fxcm_roles_jitter_kernel, dim3(FX_M_WGS + 2), dim3(FX_DEV_THREADS), FX_LDS_BYTES, s, h->d_dev, h->d_xfer, h->d_rows, d_bytes, h->d_recs[b], d_lstmpr,
+                       d_lstmex, d_probs + 3, (long)pstride, (int)nbytes, h->d_prof, h->jitter);
+  } else {
+    hipLaunchKernelGGL(cmx_fxcm_roles_kernel, dim3(FX_M_WGS + 2), dim3(FX_DEV_THREADS), FX_LDS_BYTES, s, h->d_dev, h->d_xfer, h->d_rows, d_bytes, h->d_recs[b], d_lstmpr,
+                       d_lstmex, d_probs + 3, (long)pstride, (int)nbytes, h->d_prof);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { cmx_set_err(std::string("cmx_fxcm_run: ") + hipGetErrorString(e)); return 1; }
   if (hipEventRecord(h->done[b], s) != hipSuccess) { cmx_set_err("cmx_fxcm_run: event record failed"); return 1; }
@@ -1016,7 +1055,7 @@ int cmx_fxcm_run_late(cmx_fxcm_t* h, void* box, size_t nbytes, const int16_t* hi
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   if (h->late_cap[slot] < nbytes || h->rows_cap < nbytes) { cmx_set_err("cmx_fxcm_run_late: call cmx_fxcm_late_prepare first (nothing may be allocated while the stream's kernels run)"); return 1; }
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync((char*)h->d_xfer + 16, 0, sizeof(FxXfer) - 16, s) != hipSuccess) { cmx_set_err("cmx_fxcm_run_late: hipMemsetAsync failed"); return 1; }
+  if (hipMemsetAsync((char*)h->d_xfer + 16, 0, offsetof(FxXfer, jit) - 16, s) != hipSuccess) { cmx_set_err("cmx_fxcm_run_late: hipMemsetAsync failed"); return 1; }
   hipLaunchKernelGGL(cmx_fxcm_roles_late_kernel, dim3(FX_M_WGS + 2), dim3(FX_DEV_THREADS), FX_LDS_BYTES, s, h->d_dev, h->d_xfer, h->d_rows, *(const CmxLate*)box,
                      (const FxByteRec*)h->late_drecs[slot], hint_pr, hint_ex, d_probs + 3, (long)pstride, (int)nbytes);
   hipError_t e = hipGetLastError();
@@ -1043,6 +1082,40 @@ int cmx_fxcm_late_byte(cmx_fxcm_t* h, int slot, size_t b, uint8_t byte) {
 int cmx_fxcm_profile(cmx_fxcm_t* h, unsigned long long out64[128]) {
   if (!h || !h->d_prof) return 1;
   return hipMemcpy(out64, h->d_prof, 1024, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
+}
+
+// TEST HOOK: before the first byte, continue as if blpos bytes of the block had been coded (what fxe_set_blpos does in tests/host/fxcm_emul.cpp): the device
+// model's position, once the stream's work has drained, and the parser's
+int cmx_fxcm_debug_set_blpos(cmx_fxcm_t* h, int blpos) {
+  if (!h || blpos < 0) { cmx_set_err("cmx_fxcm_debug_set_blpos: bad argument"); return 1; }
+  if (h->bytes_done) { cmx_set_err("cmx_fxcm_debug_set_blpos: the stream has begun (the position is placed before the first byte only)"); return 1; }
+  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&h->d_dev->blpos, &blpos, sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    cmx_set_err("cmx_fxcm_debug_set_blpos: device error"); return 1;
+  }
+  fxp_set_blpos(h->parser, blpos);
+  return 0;
+}
+
+// TEST HOOK (CMX_FXCM_JITTER): the stalls each site of the jitter kernel has taken since creation: [0..15] role M's wavefronts, [16] role U, [17] role X
+int cmx_fxcm_debug_jitter_counts(cmx_fxcm_t* h, unsigned out18[18]) {
+  if (!h || !out18) { cmx_set_err("cmx_fxcm_debug_jitter_counts: bad argument"); return 1; }
+  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out18, h->d_xfer->jit, sizeof(unsigned) * (FX_M_WAVES + 2), hipMemcpyDeviceToHost) != hipSuccess) {
+    cmx_set_err("cmx_fxcm_debug_jitter_counts: device error"); return 1;
+  }
+  return 0;
+}
+
+// TEST HOOK: how many launches so far found the previous launch of their staging slot (FX_STAGE_BUFS slots, taken in turn) still in flight and waited for it
+int cmx_fxcm_debug_ring_waits(cmx_fxcm_t* h) { return h ? (int)h->ring_waits : -1; }
+
+// TEST HOOK: FxDev::slot_parallel as the kernels read it from device memory (0 under CMX_FXCM_SERIAL_MAPS=1); -1 on error. Syncs.
+int cmx_fxcm_debug_slot_parallel(cmx_fxcm_t* h) {
+  if (!h || hipSetDevice(h->device) != hipSuccess) return -1;
+  int v = -1;
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, &h->d_dev->slot_parallel, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return v;
 }
 
 int cmx_fxcm_set_upload_stream(cmx_fxcm_t* h, void* stream) {

@@ -55,6 +55,10 @@ def lib():
         L.cmx_fxcm_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.cmx_fxcm_sync.argtypes = [C.c_void_p]
         L.cmx_fxcm_failed.argtypes = [C.c_void_p]
+        L.cmx_fxcm_debug_set_blpos.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_fxcm_debug_jitter_counts.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_fxcm_debug_ring_waits.argtypes = [C.c_void_p]
+        L.cmx_fxcm_debug_slot_parallel.argtypes = [C.c_void_p]
         L.cmx_mixnet_create.restype = C.c_void_p
         L.cmx_mixnet_create.argtypes = [C.c_int]
         L.cmx_mixnet_destroy.argtypes = [C.c_void_p]
@@ -1617,17 +1621,43 @@ class Fxcm:
         self.h = lib().cmx_fxcm_create(dictionary_path.encode() if isinstance(dictionary_path, str) else dictionary_path, device)
         if not self.h:
             raise CmxError(last_error())
+        self._keep = []
 
     def close(self):
         if getattr(self, "h", None):
-            lib().cmx_fxcm_destroy(self.h)
+            lib().cmx_fxcm_destroy(self.h)   # (waits for the device)
             self.h = None
+            self._keep = []
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    def debug_set_blpos(self, blpos):
+        """Test hook, before the first byte: continue as if blpos bytes of the block had been coded (device model and host parser)."""
+        if lib().cmx_fxcm_debug_set_blpos(self.h, int(blpos)):
+            raise CmxError(last_error())
+
+    def failed(self):
+        """True if a bounded in-launch wait of the roles kernel ran out (syncs)."""
+        return bool(lib().cmx_fxcm_failed(self.h))
+
+    def debug_jitter_counts(self):
+        """Test hook (CMX_FXCM_JITTER): stalls taken since creation by role M's 16 wavefronts, role U and role X (syncs)."""
+        out = (C.c_uint * 18)()
+        if lib().cmx_fxcm_debug_jitter_counts(self.h, out):
+            raise CmxError(last_error())
+        return [int(v) for v in out]
+
+    def debug_ring_waits(self):
+        """Test hook: launches so far that waited for their staging slot's previous launch, which was still in flight."""
+        return int(lib().cmx_fxcm_debug_ring_waits(self.h))
+
+    def debug_slot_parallel(self):
+        """Test hook: the model's slot_parallel word in device memory (0: one lane per map, CMX_FXCM_SERIAL_MAPS=1); syncs."""
+        return int(lib().cmx_fxcm_debug_slot_parallel(self.h))
 
     def run(self, data_host, lstmpr, lstmex, probs=None, stream=None):
         """data_host [N] u8 numpy; lstmpr [8N] i16 cuda, lstmex [8N] u8 cuda -> writes columns 3..433 of probs [8N, >=434] f32."""
@@ -1647,12 +1677,13 @@ class Fxcm:
                                 probs.shape[1], C.c_void_p(stream))
         if rc:
             raise CmxError(last_error())
-        self._keep = d_bytes   # the kernel reads it asynchronously
+        self._keep.append(d_bytes)   # the kernel reads it asynchronously: every launch's copy lives until sync() / close()
         return probs
 
     def sync(self):
         if lib().cmx_fxcm_sync(self.h):
             raise CmxError(last_error())
+        self._keep = []
 
 
 class P8Stage:

@@ -526,6 +526,17 @@ int cmx_fxcm_set_upload_stream(cmx_fxcm_t*, void* stream);   /* see cmx_mixnet_s
 /* diagnostics (CMX_FXCM_PROFILE=1 at create time): thread 0's clocks per phase of each role since creation, out[16 role + k] (role 0 = the
  * context maps' first wavefront, 1 = units, 2 = mixers; scripts/gpu_fxcm_time.py names the phases) */
 int cmx_fxcm_profile(cmx_fxcm_t*, unsigned long long out128[128]);   /* [64 + 8 bpos + k]: role M by bit position */
+/* TEST HOOK (as cmx_p8stage_debug_set_pos): before the first byte, continue as if blpos bytes of the block had been coded -- the device model's
+ * position (SSCM / APM rates, update1 :4772-4774) and the host parser's (the rules 448, 451 and 463 MB into a block). Waits for the device first;
+ * refused once the stream has begun. */
+int cmx_fxcm_debug_set_blpos(cmx_fxcm_t*, int blpos);
+/* TEST HOOK (CMX_FXCM_JITTER=seed at create time): how often each of the roles kernel's 18 stall sites has stalled since creation -- [0..15] role M's
+ * wavefronts, [16] role U, [17] role X; all zero without the switch. Syncs. */
+int cmx_fxcm_debug_jitter_counts(cmx_fxcm_t*, unsigned out18[18]);
+/* TEST HOOKS: the launches so far that found the previous launch of their record-staging slot (CMX_PIPELINE_SLOTS slots, taken in turn) still in
+ * flight and waited for it; the model's slot_parallel word as the kernels read it from device memory (0 under CMX_FXCM_SERIAL_MAPS=1; syncs). -1: error. */
+int cmx_fxcm_debug_ring_waits(cmx_fxcm_t*);
+int cmx_fxcm_debug_slot_parallel(cmx_fxcm_t*);
 
 /* ---- callers of the path: arithmetic coder + container header (HOST code) -------------------------------------
  * Replaces Encoder::Encode/Flush (src/coder/encoder.cpp:10-39), Decoder::Decoder/Decode (src/coder/decoder.cpp:3-39)
@@ -584,6 +595,7 @@ int cmx_ppmd_run(cmx_ppmd_t*, const uint8_t* bytes, size_t nbytes, float* out_pr
  *                          roles take turns on shared streams, the per-stream period grows)
  *   CMX_MIXNET_XCD=k       the mixing network's 27 workgroups on XCD k, hand-off words through that XCD's L2 (bit-exact either way)
  *   CMX_MIXNET_JITTER=1..15  test hook: pseudo-random stalls in the mixing network's roles (bit-exact by construction; tests/test_gpu_mixnet.py)
+ *   CMX_FXCM_JITTER=1..15  test hook: the same for the fxcm stage's three roles (compressor's form; tests/test_zgpu_stage_fxcm.py)
  *   (tolerance mode is NOT an environment switch: cmx_mixnet_set_tolerance / cmx_lstm_set_tolerance / cmx_pipeline_set_tolerance --
  *    no program that writes files turns it on)
  *   CMX_P8CM_SERIAL        1: paq8's table families walk every instance serially (A/B timing); 2: the ContextMap family's narrowed walk takes

@@ -143,9 +143,8 @@ def test_poisoned_lds_one_lane_per_map_vs_oracle(poison):
     compare(run_emul(emul(), data[:1200], pr, ex, [1, 7, 500, 1000], serial_maps=True, poison=poison), want, "one lane per map, poison 0x%02X" % poison)
 
 
-@pytest.mark.parametrize("flavour", ["binary", "runs", "markup"])
-def test_other_data_vs_oracle(flavour):
-    L = emul()
+def other_data_case(flavour):
+    """data and hints of test_other_data_vs_oracle (the device runs the markup flavour as well, tests/test_zgpu_stage_fxcm.py)"""
     r = np.random.default_rng(5)
     if flavour == "binary":
         data = r.integers(0, 256, 3000).astype(np.uint8)
@@ -156,15 +155,20 @@ def test_other_data_vs_oracle(flavour):
                  b"''italic'' and &Lref&N http://example.org/x J y\n", b"* item one\n* item two\n\n", b"\x0c\xc3\xa9t\x0c\xc3\xa9 1999 2001, 3.14 ", b"@she said 'hello' to him; it was theirs.\n"]
         data = np.frombuffer(b"".join(parts[int(i)] for i in r.integers(0, len(parts), 80)), np.uint8)[:3500]
     pr, ex = hints(8 * len(data), 11)
+    return data, pr, ex
+
+
+@pytest.mark.parametrize("flavour", ["binary", "runs", "markup"])
+def test_other_data_vs_oracle(flavour):
+    L = emul()
+    data, pr, ex = other_data_case(flavour)
     want = oracle_rows(data, pr, ex)
     got = run_emul(L, data, pr, ex, [512] * 8, seed=99)
     compare(got, want, flavour)
 
 
-def test_dictionary_mode_vs_oracle():
-    """WRT codewords (bytes >= 128) decoded through cmix's dictionary feed the stemmer; the dictionary travels with the
-    fixtures as a small stand-in (one word per line)."""
-    L = emul()
+def dictionary_case():
+    """data, hints and the path of a stand-in dictionary (one word per line; the caller unlinks it) for the dictionary-mode tests, host and device"""
     import tempfile
     words = ["the", "of", "and", "text", "math", "page", "category", "image", "running", "houses", "quickly", "nowiki", "pre", "wikipedia"] + ["w%dx" % i for i in range(200)]
     with tempfile.NamedTemporaryFile("w", suffix=".dic", delete=False) as f:
@@ -183,9 +187,19 @@ def test_dictionary_mode_vs_oracle():
         toks.append(b" " if r.random() < 0.8 else b"\n")
     data = np.frombuffer(b"".join(toks), np.uint8)[:2500]
     pr, ex = hints(8 * len(data), 13)
-    want = oracle_rows(data, pr, ex, dictionary=path)
-    got = run_emul(L, data, pr, ex, [300] * 10, dictionary=path)
-    os.unlink(path.decode())
+    return data, pr, ex, path
+
+
+def test_dictionary_mode_vs_oracle():
+    """WRT codewords (bytes >= 128) decoded through cmix's dictionary feed the stemmer; the dictionary travels with the
+    fixtures as a small stand-in (one word per line)."""
+    L = emul()
+    data, pr, ex, path = dictionary_case()
+    try:
+        want = oracle_rows(data, pr, ex, dictionary=path)
+        got = run_emul(L, data, pr, ex, [300] * 10, dictionary=path)
+    finally:
+        os.unlink(path.decode())
     compare(got, want, "dictionary mode")
 
 
@@ -214,28 +228,88 @@ def test_golden_columns(name):
     compare(got, np.ascontiguousarray(probs[:, 3:434]), name)
 
 
-def test_pretraining_then_data_vs_oracle():
-    """Predictor::Pretrain drives fxcm over the dictionary with the hints at their start-up value 0 (predictor.cpp:359,
-    471-476); the coded data follows in the same model."""
+def pretraining_case():
+    """a word list driven with the hints at 0 (as Predictor::Pretrain does), then text with seeded hints: data, hints, and the cuts (the first is the word list)"""
     from cmix_amd import synth
-    L = emul()
     data = np.frombuffer(b"aardvark\nabacus\nabandon\nability\nzebra\n" * 20 + synth.enwik_like(1500, 8), np.uint8)
     npre = 8 * 41 * 20
     pr, ex = hints(8 * len(data), 21)
     pr[:npre] = 0
     ex[:npre] = 0
-    compare(run_emul(L, data, pr, ex, [41 * 20, 700, 800]), oracle_rows(data, pr, ex), "pretraining + data")
+    return data, pr, ex, [41 * 20, 700, 800]
+
+
+def test_pretraining_then_data_vs_oracle():
+    """Predictor::Pretrain drives fxcm over the dictionary with the hints at their start-up value 0 (predictor.cpp:359,
+    471-476); the coded data follows in the same model."""
+    L = emul()
+    data, pr, ex, chunks = pretraining_case()
+    compare(run_emul(L, data, pr, ex, chunks), oracle_rows(data, pr, ex), "pretraining + data")
 
 
 @pytest.mark.parametrize("blpos", [14 * 256 * 1024 - 900, 28 * 512 * 1024 - 900, 448131719 - 700, 463139793 - 700])
 def test_block_position_thresholds_vs_oracle(blpos):
     """The SSCM / APM rates change 3.67 MB and 14.7 MB into the block, two parser rules 448 MB and 463 MB in (update1
-    :4772-4774, modelPrediction :3866, :3932): the stream starts just before each threshold."""
+    :4772-4774, modelPrediction :3866, :3932): the stream starts just before each threshold. (This stream does not react to every
+    threshold; test_block_position_thresholds_vs_oracle_cut_layouts runs all five on one that does.)"""
     from cmix_amd import synth
     L = emul()
     data = np.frombuffer(synth.enwik_like(1800, 4), np.uint8)
     pr, ex = hints(8 * len(data), 17)
     compare(run_emul(L, data, pr, ex, [600] * 3, blpos=blpos), oracle_rows(data, pr, ex, blpos=blpos), "blpos %d" % blpos)
+
+
+# ---- every threshold on a stream that reacts to it, cut three ways -------------------------------------------------------------------------
+# The five places fxcm reads its position in the block: the SSCM / APM rates (update1 :4772-4774) and three parser rules -- the codeword
+# context (:3866 / :3932), the stemmer's auxiliary-verb list (:3198, fxcm_parser_host.cpp fx_stem) and the conjunction rule (:3965).
+THRESHOLDS = [14 * 256 * 1024, 28 * 512 * 1024, 448131719, 451531986, 463139793]
+THRESHOLD_BACK = 700    # the stream starts this many bytes below the threshold: the first update with blpos > T is the boundary bit of stream byte 700
+# the crossing in mid-launch | stream byte 700 is a launch's last byte | byte 700 and byte 701 are each a launch of their own
+THRESHOLD_CUTS = {"mid": [600, 600, 600], "last": [701, 1099], "alone": [700, 1, 1, 1098]}
+_THRESHOLD_TEXT = (b"the cat sat and the dog ran but it was late; however he has been there, and she is going. they were happy or sad, yet we have seen it. "
+                   b"it will be done because you can do it although I am not sure.\n")
+_threshold_ref = {}
+
+
+def threshold_stream(n=1800):
+    """Text in which every rule that depends on the position has something to decide after the crossing: auxiliary verbs, conjunctions and
+    conjunctive adverbs at word ends, words for the codeword context; with it the hints."""
+    from cmix_amd import synth
+    data = np.frombuffer((synth.enwik_like(600, 4) + _THRESHOLD_TEXT * 12)[:1800], np.uint8)[:n]
+    pr, ex = hints(8 * 1800, 17)
+    return data, pr[:8 * n], ex[:8 * n]
+
+
+def threshold_case(threshold, back=THRESHOLD_BACK):
+    """the stream, its hints and the oracle's rows for a start `back` bytes below the threshold: computed once for the cut layouts of a test, which
+    run one after the other (only the last threshold's rows are kept, 25 MB: a set per threshold would stay for the rest of the process)"""
+    key = (threshold, back)
+    if key not in _threshold_ref:
+        data, pr, ex = threshold_stream()
+        _threshold_ref.clear()
+        _threshold_ref[key] = (data, pr, ex, oracle_rows(data, pr, ex, blpos=threshold - back))
+    return _threshold_ref[key]
+
+
+@pytest.mark.parametrize("threshold", THRESHOLDS)
+def test_the_thresholds_matter(threshold):
+    """The threshold cases would be worthless on a stream that does not react: the oracle's rows for a start 700 bytes below the threshold must
+    differ from those for a start 65 536 bytes lower (which crosses nothing) -- and not before bit 8 * 700, so the difference is the
+    crossing's and not the start position's."""
+    data, pr, ex, rows = threshold_case(threshold)
+    low = oracle_rows(data, pr, ex, blpos=threshold - THRESHOLD_BACK - 65536)
+    differs = np.nonzero((rows.view(np.uint32) != low.view(np.uint32)).any(axis=1))[0]
+    print("threshold %d: first differing bit %s, %d differing rows" % (threshold, differs[:1], differs.size))
+    assert differs.size > 0, "the stream does not react to the threshold at %d" % threshold
+    assert differs[0] >= 8 * THRESHOLD_BACK, (threshold, "rows differ before the crossing, first at bit", int(differs[0]))
+
+
+@pytest.mark.parametrize("cuts", sorted(THRESHOLD_CUTS))
+@pytest.mark.parametrize("threshold", THRESHOLDS)
+def test_block_position_thresholds_vs_oracle_cut_layouts(threshold, cuts):
+    """All five thresholds on the stream of test_the_thresholds_matter, the crossing in mid-launch, as a launch's last byte and as a launch of its own."""
+    data, pr, ex, want = threshold_case(threshold)
+    compare(run_emul(emul(), data, pr, ex, THRESHOLD_CUTS[cuts], blpos=threshold - THRESHOLD_BACK), want, "threshold %d, cuts %s" % (threshold, cuts))
 
 
 def _reference_fixture(name):

@@ -363,20 +363,27 @@ def test_whole_fxcm_model_vs_reference_across_block_position_thresholds(blpos, t
     """fxcm reads its position in the block at five places: the SSCM / APM rates step at 3.67 MB and 14.7 MB (update1, fxcmv1.cpp:4772-4774) and
     modelPrediction changes three decisions between 448 MB and 463 MB (:3200, :3918 / :3929, :3965). The 4 and 8 MiB files cross the first for real;
     the others lie beyond every stream that was ever run here. State injection (round 6's wrap / threshold audit): the reference's own
-    fxcmv1::Predictor and the oracle are both placed shortly before each threshold and run across it -- all 431 values after every bit. The stage's
-    host bodies and device kernels are pinned on the oracle at the same places (tests/test_fxcm_stage_host.py, test_zgpu_stage_fxcm.py)."""
-    from cmix_amd import synth
+    fxcmv1::Predictor and the oracle are both placed shortly before each threshold and run across it -- all 431 values after every bit. The stream
+    is the one of tests/test_fxcm_stage_host.py::test_the_thresholds_matter, which reacts to every one of the five, and the same guard runs here on
+    the oracle's side: a second oracle model started 65 536 bytes lower must differ from the first, and not before the crossing. The stage's host
+    bodies are pinned on the oracle at the same thresholds by test_fxcm_stage_host.py::test_block_position_thresholds_vs_oracle and
+    ::test_block_position_thresholds_vs_oracle_cut_layouts, the device kernels by test_zgpu_stage_fxcm.py::test_block_position_thresholds_vs_oracle."""
+    from test_fxcm_stage_host import THRESHOLDS, threshold_stream
     L, lib = _private_fx_copy(tmp_path), O.lib()
     lib.orc_fx_model_new.restype = P
     lib.orc_fx_model_update.argtypes = [P, C.c_int, C.c_int, C.c_int, P]
     lib.orc_fx_model_set_blpos.argtypes = [P, C.c_int]
     L.reffx_model_set_blpos.argtypes = [P, C.c_int]
     rng = np.random.default_rng(blpos & 0xffff)
-    data = synth.enwik_like(1400, 61, rich=True)
-    ref, got = L.reffx_model_new(), lib.orc_fx_model_new()
+    data = threshold_stream(1400)[0].tobytes()
+    back = min(t for t in THRESHOLDS if t > blpos) - blpos   # the crossing: the first update with blpos > threshold is the boundary bit of stream byte `back`
+    ref = L.reffx_model_new()
+    (got, tag_got), (low, tag_low) = O.new_owned(lib.orc_fx_model_new), O.new_owned(lib.orc_fx_model_new)   # (the oracle's two models are released below)
     L.reffx_model_set_blpos(ref, blpos)
     lib.orc_fx_model_set_blpos(got, blpos)
-    a, b = np.zeros(431, np.float32), np.zeros(431, np.float32)
+    lib.orc_fx_model_set_blpos(low, blpos - 65536)
+    a, b, c = np.zeros(431, np.float32), np.zeros(431, np.float32), np.zeros(431, np.float32)
+    differs = []   # rows (row q + 1 = what update q returns) in which the model started lower, which crosses nothing, differs
     for n, byte in enumerate(data):
         for bpos in range(8):
             y = (byte >> (7 - bpos)) & 1
@@ -384,6 +391,14 @@ def test_whole_fxcm_model_vs_reference_across_block_position_thresholds(blpos, t
             pr, pg = L.reffx_model_update(ref, y, hp, hx, a.ctypes.data), lib.orc_fx_model_update(got, y, hp, hx, b.ctypes.data)
             bad = np.nonzero(a.view(np.uint32) != b.view(np.uint32))[0]
             assert bad.size == 0 and pr == pg, (blpos, n, bpos, bad[:8], pr, pg)
+            lib.orc_fx_model_update(low, y, hp, hx, c.ctypes.data)
+            if (b.view(np.uint32) != c.view(np.uint32)).any():
+                differs.append(8 * n + bpos + 1)
+    O.release(tag_got)
+    O.release(tag_low)
+    print("start %d: first differing row %s, %d differing rows" % (blpos, differs[:1], len(differs)))
+    assert differs, "the stream does not react to the threshold %d bytes ahead of %d" % (back, blpos)
+    assert differs[0] >= 8 * back, (blpos, "rows differ before the crossing, first at bit", differs[0])
 
 
 DICTIONARY = os.path.join(ROOT, "oracle", "_ref", "english.dic")   # the reference's dictionary, copied by `make -C oracle ref`
