@@ -89,6 +89,7 @@ struct cmx_engine {
   int ctx_shadow = 0;             // cmx_set_ctx_shadow: shadow context stages of the look-ahead pipeline, voting on every chunk
   struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t lane = 0, index = 0; uint32_t mask = 0; } dbg_cxor;   // cmx_debug_ctx_shadow_xor
   int lstm_shadow = 0;            // cmx_set_lstm_shadow: shadow LSTM stages of the look-ahead pipeline, voting on every chunk
+  int fxcm_shadow = 0;            // cmx_set_fxcm_shadow: shadow fxcm stages of the look-ahead pipeline, voting on every chunk
   int journal = 0;                // cmx_set_journal: log2 of the stream journal's block (0 = off): the look-ahead pipeline's kernel, or a decoder's host-side fold
   CmxHostJournal* hj = nullptr;   // a decoder's journal (mode 3): the p and bits words, folded on this thread bit by bit
   std::vector<std::array<uint64_t, 3>> jr_want; bool jr_check = false;   // cmx_set_journal_check: a compressor's journal to hold the decode to
@@ -343,6 +344,7 @@ int ensure_lookahead(cmx_engine* h) {
             (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0) &&
             (!h->ctx_shadow || cmx_pipeline_set_ctx_shadow(la->pipe, h->ctx_shadow) == 0) &&   // (before the pretraining below: every instance learns the dictionary)
             (!h->lstm_shadow || cmx_pipeline_set_lstm_shadow(la->pipe, h->lstm_shadow) == 0) &&
+            (!h->fxcm_shadow || cmx_pipeline_set_fxcm_shadow(la->pipe, h->fxcm_shadow) == 0) &&   // (before the pretraining below as well: fxcm learns the dictionary)
             (!h->journal || cmx_pipeline_set_journal(la->pipe, h->journal) == 0);
   if (ok && h->jr_check) { cmx_set_err("cmx_stage_input: a journal to check against is set (cmx_set_journal_check), which covers a decoder only"); ok = false; }
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
@@ -830,6 +832,19 @@ int cmx_set_lstm_shadow(cmx_t* h, int k) {
   if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_lstm_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
   h->lstm_shadow = k;
   return 0;
+}
+// shadow fxcm stages of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
+int cmx_set_fxcm_shadow(cmx_t* h, int k) {
+  if (!h) { cmx_set_err("cmx_set_fxcm_shadow: null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err("cmx_set_fxcm_shadow: k must be 0, 1 or 2 shadow fxcm stages"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_fxcm_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  h->fxcm_shadow = k;
+  return 0;
+}
+int cmx_fxcm_shadow_report(cmx_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_fxcm_shadow_report: bad argument"); return 1; }
+  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
+  return cmx_pipeline_fxcm_shadow_report(h->la->pipe, out);
 }
 int cmx_lstm_shadow_report(cmx_t* h, uint64_t out[8]) {
   if (!h || !out) { cmx_set_err("cmx_lstm_shadow_report: bad argument"); return 1; }

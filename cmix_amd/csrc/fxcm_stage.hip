@@ -12,12 +12,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
 
 #include "../../include/cmix_amd.h"
 #include "fxcm_build.h"
+#include "fxcm_state.h"
 #include "cmx_late.h"
 #include "cmx_streams.h"
 
@@ -879,11 +881,13 @@ static const size_t FX_LDS_BYTES = ((sizeof(FxShared) + 15) & ~(size_t)15) + siz
 namespace {
 struct DevPolicy {
   std::vector<void*> blocks;
+  std::vector<size_t> sizes;   // bytes asked for, block by block: two handles built by the same fxb::build pair up array by array (cmx_fxcm_state_view)
   bool ok = true;
   void* zalloc(size_t bytes) {
     void* p = nullptr;
     if (!ok || hipMalloc(&p, bytes + 64) != hipSuccess || hipMemset(p, 0, bytes + 64) != hipSuccess) { ok = false; return nullptr; }
     blocks.push_back(p);
+    sizes.push_back(bytes);
     return p;
   }
   void fill16(void* p, size_t n, uint16_t v) { if (p && hipMemsetD16((hipDeviceptr_t)p, v, n) != hipSuccess) ok = false; }
@@ -920,6 +924,14 @@ struct cmx_fxcm {
   hipStream_t s_up = nullptr; bool own_up = false;   // record uploads: a stream that never has a kernel in front of a copy (cmx_fxcm_set_upload_stream)
   hipEvent_t ev_up[FX_STAGE_BUFS] = {};
   unsigned ring_waits = 0;   // launches that found their staging slot's previous launch still in flight (cmx_fxcm_debug_ring_waits)
+  // shadow instances (cmx_fxcm_create_shadow / cmx_fxcm_run_shared): a shadow has no parser and reads its owner's uploaded records; the owner keeps, per
+  // staging slot and reader, the event behind the reader's launch on that slot and refills the slot only when those have completed as well
+  bool is_shadow = false;
+  cmx_fxcm* owner = nullptr;               // (a shadow's) the handle whose records it read last; unlinked when either is destroyed
+  cmx_fxcm* readers[2] = {nullptr, nullptr};
+  hipEvent_t rd[FX_STAGE_BUFS][2] = {};    // created when the first reader registers
+  bool rd_used[FX_STAGE_BUFS][2] = {};
+  int last = -1; size_t last_n = 0;        // the staging slot and size of the most recent cmx_fxcm_run
   int jitter = 0;   // CMX_FXCM_JITTER=1..15 (test hook, tests/test_zgpu_stage_fxcm.py): pseudo-random stalls in every role -- same results, every lead / lag between the roles
   FxByteRec* late_recs[3] = {}; FxByteRec* late_drecs[3] = {}; size_t late_cap[3] = {};   // the decoder's form (cmx_late.h): host-coherent records and their device mirrors (the relay wave copies a byte's record over when the byte is complete), three chunk slots
 };
@@ -930,6 +942,9 @@ void cmx_fxcm_destroy(cmx_fxcm_t* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
+  if (h->owner) for (cmx_fxcm*& r : h->owner->readers) if (r == h) r = nullptr;
+  for (cmx_fxcm* r : h->readers) if (r) r->owner = nullptr;
+  for (auto& slot : h->rd) for (hipEvent_t e : slot) if (e) (void)hipEventDestroy(e);
   for (void* p : h->pol.blocks) (void)hipFree(p);
   if (h->d_dev) (void)hipFree(h->d_dev);
   for (int i = 0; i < FX_STAGE_BUFS; i++) {
@@ -948,8 +963,9 @@ void cmx_fxcm_destroy(cmx_fxcm_t* h) {
   delete h;
 }
 
-cmx_fxcm_t* cmx_fxcm_create(const char* dictionary_path, int device) {
-  if (cmx_device_count() <= 0) { cmx_set_err("cmx_fxcm_create: no HIP device visible (a gfx950 GPU is required)"); return nullptr; }
+// the device half of a handle: the tables of fxb::build, the hand-off block, the events. `what`: the caller's name for messages
+static cmx_fxcm_t* fx_create_device(int device, const char* what) {
+  if (cmx_device_count() <= 0) { cmx_set_err(std::string(what) + ": no HIP device visible (a gfx950 GPU is required)"); return nullptr; }
   if (hipSetDevice(device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return nullptr; }
   cmx_fxcm_t* h = new cmx_fxcm();
   h->device = device;
@@ -969,8 +985,20 @@ cmx_fxcm_t* cmx_fxcm_create(const char* dictionary_path, int device) {
   const char* prof = getenv("CMX_FXCM_PROFILE");
   if (ok && prof && prof[0] == '1') ok = hipMalloc((void**)&h->d_prof, 1024) == hipSuccess && hipMemset(h->d_prof, 0, 1024) == hipSuccess;
   ok = ok && hipDeviceSynchronize() == hipSuccess;
-  if (!ok) { cmx_set_err("cmx_fxcm_create: allocation / init failed (the stage needs ~4.4 GB of HBM)"); cmx_fxcm_destroy(h); return nullptr; }
-  h->parser = fxp_create(dictionary_path);
+  if (!ok) { cmx_set_err(std::string(what) + ": allocation / init failed (the stage needs ~4.4 GB of HBM)"); cmx_fxcm_destroy(h); return nullptr; }
+  return h;
+}
+
+cmx_fxcm_t* cmx_fxcm_create(const char* dictionary_path, int device) {
+  cmx_fxcm_t* h = fx_create_device(device, "cmx_fxcm_create");
+  if (h) h->parser = fxp_create(dictionary_path);
+  return h;
+}
+
+// A shadow instance (include/cmix_amd.h): the same device state, built by the same fxb::build (which reads no dictionary), and no parser
+cmx_fxcm_t* cmx_fxcm_create_shadow(int device) {
+  cmx_fxcm_t* h = fx_create_device(device, "cmx_fxcm_create_shadow");
+  if (h) h->is_shadow = true;
   return h;
 }
 
@@ -979,12 +1007,18 @@ int cmx_fxcm_run(cmx_fxcm_t* h, const uint8_t* bytes, const uint8_t* d_bytes, si
   if (!h) { cmx_set_err("cmx_fxcm_run: null handle"); return 1; }
   if (nbytes == 0) return 0;
   if (!bytes || !d_bytes || !d_lstmpr || !d_lstmex || !d_probs || pstride < 3 + FX_OUTPUTS || nbytes > (1u << 24)) { cmx_set_err("cmx_fxcm_run: bad argument"); return 1; }
+  if (h->is_shadow) { cmx_set_err("cmx_fxcm_run: a shadow instance has no parser (cmx_fxcm_run_shared runs it on its owner's records)"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   const int b = h->next;
   h->next = (h->next + 1) % FX_STAGE_BUFS;
   if (h->used[b]) {
-    if (hipEventQuery(h->done[b]) == hipErrorNotReady) { h->ring_waits++; (void)hipGetLastError(); }   // (counted for the tests; "not ready" is no error of the stream's)
-    if (hipEventSynchronize(h->done[b]) != hipSuccess) { cmx_set_err("cmx_fxcm_run: staging buffer wait failed"); return 1; }
+    // the slot's previous launch AND every shadow launch that read its records (done[b] knows only this handle's kernel)
+    bool busy = hipEventQuery(h->done[b]) == hipErrorNotReady;
+    for (int r = 0; r < 2; r++) if (h->rd_used[b][r] && hipEventQuery(h->rd[b][r]) == hipErrorNotReady) busy = true;
+    if (busy) { h->ring_waits++; (void)hipGetLastError(); }   // (counted for the tests, once per launch; "not ready" is no error of the stream's)
+    bool ok = hipEventSynchronize(h->done[b]) == hipSuccess;
+    for (int r = 0; r < 2; r++) if (h->rd_used[b][r]) { ok = hipEventSynchronize(h->rd[b][r]) == hipSuccess && ok; h->rd_used[b][r] = false; }
+    if (!ok) { cmx_set_err("cmx_fxcm_run: staging buffer wait failed"); return 1; }
   }
   if (h->cap[b] < nbytes) {
     if (h->h_recs[b]) (void)hipHostFree(h->h_recs[b]);
@@ -1021,6 +1055,59 @@ int cmx_fxcm_run(cmx_fxcm_t* h, const uint8_t* bytes, const uint8_t* d_bytes, si
   if (e != hipSuccess) { cmx_set_err(std::string("cmx_fxcm_run: ") + hipGetErrorString(e)); return 1; }
   if (hipEventRecord(h->done[b], s) != hipSuccess) { cmx_set_err("cmx_fxcm_run: event record failed"); return 1; }
   h->used[b] = true;
+  h->last = b; h->last_n = nbytes;
+  h->bytes_done += nbytes;
+  return 0;
+}
+
+// A shadow's launch on the records of the owner's most recent cmx_fxcm_run (include/cmix_amd.h): the unchanged roles kernel on the shadow's own FxDev,
+// row buffer, FxXfer and fail flag; `stream` waits for that slot's upload, and the owner's slot learns of this reader.
+int cmx_fxcm_run_shared(cmx_fxcm_t* h, cmx_fxcm_t* owner, const uint8_t* d_bytes, size_t nbytes, const int16_t* d_lstmpr, const uint8_t* d_lstmex,
+                        float* d_probs, size_t pstride, void* stream) {
+  if (!h || !owner) { cmx_set_err("cmx_fxcm_run_shared: null handle"); return 1; }
+  if (!h->is_shadow || owner->is_shadow) { cmx_set_err("cmx_fxcm_run_shared: the first handle must be a shadow (cmx_fxcm_create_shadow), the second one with a parser (cmx_fxcm_create)"); return 1; }
+  if (h->device != owner->device) { cmx_set_err("cmx_fxcm_run_shared: the shadow and its owner live on different devices"); return 1; }
+  if (nbytes == 0) return 0;
+  if (!d_bytes || !d_lstmpr || !d_lstmex || !d_probs || pstride < 3 + FX_OUTPUTS) { cmx_set_err("cmx_fxcm_run_shared: bad argument"); return 1; }
+  if (owner->last < 0 || owner->last_n != nbytes) { cmx_set_err("cmx_fxcm_run_shared: the owner's most recent cmx_fxcm_run was not a chunk of " + std::to_string(nbytes) + " bytes"); return 1; }
+  if (h->bytes_done + nbytes != owner->bytes_done) {
+    cmx_set_err("cmx_fxcm_run_shared: the shadow has run " + std::to_string(h->bytes_done) + " bytes and the owner " + std::to_string(owner->bytes_done - nbytes) +
+                " before this chunk (a shadow runs every chunk of its owner, once)");
+    return 1;
+  }
+  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  int r = owner->readers[0] == h ? 0 : owner->readers[1] == h ? 1 : -1;
+  if (r < 0) {
+    r = !owner->readers[0] ? 0 : !owner->readers[1] ? 1 : -1;
+    if (r < 0) { cmx_set_err("cmx_fxcm_run_shared: the owner has two shadows already"); return 1; }
+    if (h->owner && h->owner != owner) { cmx_set_err("cmx_fxcm_run_shared: the shadow belongs to another owner"); return 1; }
+    for (int i = 0; i < FX_STAGE_BUFS; i++)
+      if (!owner->rd[i][r] && hipEventCreateWithFlags(&owner->rd[i][r], hipEventDisableTiming) != hipSuccess) { cmx_set_err("cmx_fxcm_run_shared: event creation failed"); return 1; }
+    owner->readers[r] = h; h->owner = owner;
+    if (owner->jitter) { h->jitter = (owner->jitter + 5 * (r + 1)) & 15; if (!h->jitter) h->jitter = 1; }   // test hook: every instance stalls at other moments
+  }
+  const int b = owner->last;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipStreamWaitEvent(s, owner->ev_up[b], 0) != hipSuccess) { cmx_set_err("cmx_fxcm_run_shared: wait for the record upload failed"); return 1; }
+  if (h->rows_cap < nbytes) {   // grown between chunks: nothing of this instance may be in flight on the old buffer
+    if (hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_fxcm_run_shared: device error"); return 1; }
+    if (h->d_rows) (void)hipFree(h->d_rows);
+    h->d_rows = nullptr; h->rows_cap = 0;
+    if (hipMalloc((void**)&h->d_rows, nbytes * 8 * FX_ROW_WORDS * 4) != hipSuccess) { cmx_set_err("cmx_fxcm_run_shared: row buffer allocation failed"); return 1; }
+    h->rows_cap = nbytes;
+  }
+  if (hipMemsetAsync((char*)h->d_xfer + 16, 0, offsetof(FxXfer, jit) - 16, s) != hipSuccess) { cmx_set_err("cmx_fxcm_run_shared: hipMemsetAsync failed"); return 1; }
+  if (h->jitter) {
+    hipLaunchKernelGGL(cmx_fxcm_roles_jitter_kernel, dim3(FX_M_WGS + 2), dim3(FX_DEV_THREADS), FX_LDS_BYTES, s, h->d_dev, h->d_xfer, h->d_rows, d_bytes, owner->d_recs[b], d_lstmpr,
+                       d_lstmex, d_probs + 3, (long)pstride, (int)nbytes, h->d_prof, h->jitter);
+  } else {
+    hipLaunchKernelGGL(cmx_fxcm_roles_kernel, dim3(FX_M_WGS + 2), dim3(FX_DEV_THREADS), FX_LDS_BYTES, s, h->d_dev, h->d_xfer, h->d_rows, d_bytes, owner->d_recs[b], d_lstmpr,
+                       d_lstmex, d_probs + 3, (long)pstride, (int)nbytes, h->d_prof);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { cmx_set_err(std::string("cmx_fxcm_run_shared: ") + hipGetErrorString(e)); return 1; }
+  if (hipEventRecord(owner->rd[b][r], s) != hipSuccess) { cmx_set_err("cmx_fxcm_run_shared: event record failed"); return 1; }
+  owner->rd_used[b][r] = true;
   h->bytes_done += nbytes;
   return 0;
 }
@@ -1032,6 +1119,7 @@ int cmx_fxcm_run(cmx_fxcm_t* h, const uint8_t* bytes, const uint8_t* d_bytes, si
 // everything the decoder's form allocates, for chunks of up to nbytes bytes: before the first chunk's kernels are launched
 int cmx_fxcm_late_prepare(cmx_fxcm_t* h, size_t nbytes) {
   if (!h || nbytes == 0 || nbytes > (1u << 16)) { cmx_set_err("cmx_fxcm_late_prepare: bad argument"); return 1; }
+  if (h->is_shadow) { cmx_set_err("cmx_fxcm_late_prepare: a shadow instance has no parser (a decoder is not covered)"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   for (int slot = 0; slot < 3; slot++) {
     if (h->late_cap[slot] >= nbytes) continue;
@@ -1089,6 +1177,7 @@ int cmx_fxcm_profile(cmx_fxcm_t* h, unsigned long long out64[128]) {
 int cmx_fxcm_debug_set_blpos(cmx_fxcm_t* h, int blpos) {
   if (!h || blpos < 0) { cmx_set_err("cmx_fxcm_debug_set_blpos: bad argument"); return 1; }
   if (h->bytes_done) { cmx_set_err("cmx_fxcm_debug_set_blpos: the stream has begun (the position is placed before the first byte only)"); return 1; }
+  if (h->is_shadow) { cmx_set_err("cmx_fxcm_debug_set_blpos: a shadow instance has no parser to place"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&h->d_dev->blpos, &blpos, sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
     cmx_set_err("cmx_fxcm_debug_set_blpos: device error"); return 1;
@@ -1147,3 +1236,55 @@ int cmx_fxcm_sync(cmx_fxcm_t* h) {
 }
 
 }  // extern "C"
+
+// ---- the state view (fxcm_state.h; walked by cmx_fxcm_state_diff, _debug_state_xor and _debug_layout in fxcm_vote.hip) ----
+// fxb::build asks its policy for 140 blocks in a fixed order: squash, stretch, wrt, the six state tables; per map its buckets, its lookup table `tab`
+// and its StateMaps; 7 SSCM tables; 3 sm1_t; rcm_t; mhash; sp_table; buffer; 12 wx; per APM its table and the 33-entry pattern it was filled from.
+// block_region names each block's region; the view lists region 0's blocks first, then region 1's, ... each in build order.
+static int fx_block_region(int i) {
+  if (i < 9) return 0;
+  i -= 9;
+  if (i < 3 * FX_NMAPS) return i % 3 == 0 ? 1 : i % 3 == 1 ? 0 : 2;
+  i -= 3 * FX_NMAPS;
+  if (i < FX_NSSCM) return 3;
+  i -= FX_NSSCM;
+  if (i < 3) return 4;
+  i -= 3;
+  if (i < 4) return 5 + i;   // rcm_t, mhash, sp_table, buffer
+  i -= 4;
+  if (i < 12) return 9;
+  i -= 12;
+  return i % 2 == 0 ? 10 : 0;
+}
+int cmx_fxcm_state_view(cmx_fxcm* h, FxRegion* out, int* n, int* device, uint64_t* bytes_done) {
+  if (!h || !out || !n || !device) { cmx_set_err("cmx_fxcm_state_view: bad argument"); return 1; }
+  const int nb = (int)h->pol.blocks.size();
+  if (nb != FX_STATE_ARRAYS - 1 || h->pol.sizes.size() != h->pol.blocks.size()) { cmx_set_err("cmx_fxcm_state_view: internal layout error"); return 1; }
+  int k = 0;
+  for (int r = 0; r < FX_REGION_DEV; r++)
+    for (int i = 0; i < nb; i++)
+      if (fx_block_region(i) == r) { out[k].region = r; out[k].p = (uint32_t*)h->pol.blocks[i]; out[k].words = (h->pol.sizes[i] + 3) / 4; ++k; }   // (a block is 64 zero bytes longer than asked for)
+  *n = k; *device = h->device;
+  if (bytes_done) *bytes_done = h->bytes_done;
+  return 0;
+}
+int cmx_fxcm_dev_words(cmx_fxcm* h, std::vector<uint32_t>& out) {
+  static_assert(sizeof(FxDev) % 4 == 0, "FxDev is compared as whole words");
+  if (!h) { cmx_set_err("cmx_fxcm_dev_words: null handle"); return 1; }
+  out.resize(sizeof(FxDev) / 4);
+  FxDev& c = *reinterpret_cast<FxDev*>(out.data());
+  if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&c, h->d_dev, sizeof(FxDev), hipMemcpyDeviceToHost) != hipSuccess) {
+    cmx_set_err("cmx_fxcm_dev_words: device error"); return 1;
+  }
+  // device pointers differ between two handles by construction
+  for (FxMapDev& x : c.maps) { x.t = nullptr; x.nn = nullptr; x.tab = nullptr; x.sm = nullptr; }
+  c.squash = nullptr; c.stretch = nullptr; c.wrt = nullptr;
+  for (const uint8_t*& p : c.sta) p = nullptr;
+  for (auto& p : c.sscm_data) p = nullptr;
+  for (auto& p : c.sm1_t) p = nullptr;
+  c.rcm_t = nullptr; c.mhash = nullptr; c.sp_table = nullptr; c.buffer = nullptr;
+  for (auto& p : c.wx) p = nullptr;
+  for (auto& p : c.apm_t) p = nullptr;
+  for (FxMatchInfo& m : c.cand) memset((char*)&m + offsetof(FxMatchInfo, delta) + 1, 0, sizeof(FxMatchInfo) - offsetof(FxMatchInfo, delta) - 1);   // (padding: a candidate is assigned as a whole in the kernel)
+  return 0;
+}

@@ -148,6 +148,11 @@ struct Slot {
   unsigned long long* h_lsvote = nullptr;              // pinned [12]: the LSTM vote's record as it stood behind this chunk, then the chunk's own result; then the shadows' two sticky hand-off flags
   hipEvent_t ev_ls[2] = {nullptr, nullptr}, ev_lsvote = nullptr;
   bool lsvoted = false;                                // this slot's chunk has an LSTM vote behind it: slot_done waits for ev_lsvote too
+  // shadow fxcm stages (cmx_pipeline_set_fxcm_shadow): allocated at the first begin (or pretrain), nothing of it otherwise
+  float* d_fsp[2] = {nullptr, nullptr};                // [8 max][434] rows of shadow i + 1 (columns 3..433 used)
+  unsigned long long* h_fsvote = nullptr;              // pinned [12]: the fxcm vote's record as it stood behind this chunk, then the chunk's own result; then the shadows' two sticky hand-off flags
+  hipEvent_t ev_fs[2] = {nullptr, nullptr}, ev_fsvote = nullptr;
+  bool fsvoted = false;                                // this slot's chunk has an fxcm vote behind it: slot_done waits for ev_fsvote too (the vote reads the slot's layer-0 rows in place)
   // stream journal (cmx_pipeline_set_journal): allocated at the set call, nothing of it otherwise
   unsigned long long* d_jr = nullptr;                  // the chunk's partial records on the device
   uint64_t* h_jr = nullptr;                            // pinned: their copy, complete when ev_jr is
@@ -257,6 +262,12 @@ struct cmx_pipeline {
   cmx_lstm_t* ls[2] = {nullptr, nullptr};         // created at the first begin
   cmx_lstmvote_t* lsvote = nullptr;
   uint64_t lsvote_bytes = 0;     // stream bytes handed to the LSTM vote so far
+  int fxcm_shadow = 0;           // cmx_pipeline_set_fxcm_shadow: shadow fxcm stages beside h->fxcm (0 = off: nothing below exists)
+  hipStream_t s_fs[2] = {nullptr, nullptr};       // their streams (from the factory, at set_fxcm_shadow: the queue budget refuses there)
+  cmx_fxcm_t* fs[2] = {nullptr, nullptr};         // shadow handles without a parser, created at the first begin or at pretrain
+  float* d_fs_scratch[2] = {nullptr, nullptr};    // pretraining writes each shadow's (discarded) rows here
+  cmx_fxcmvote_t* fsvote = nullptr;
+  uint64_t fsvote_bits = 0;      // stream bits handed to the fxcm vote so far
   bool pretrained = false;       // cmx_pipeline_pretrain has run: shadow context stages set after it would start untrained
   float* dbg_mix = nullptr;      // diagnosis (cmx_pipeline_debug_mix_out): the 47 mixer outputs of every bit, [bit][47], as far as dbg_mix_cap bits
   uint64_t dbg_mix_cap = 0, dbg_mix_bits = 0;
@@ -286,12 +297,13 @@ void collect(cmx_pipeline* h, Slot& s) {  // the slot's chunk has finished (its 
 // The overlap probe on every stream of the handle (include/cmix_amd.h, cmx_pipeline_stage_overlap): the stage streams, the upload stream,
 // paq8's role streams and, in a decoder, the byte model's.
 static int probe_streams(cmx_pipeline* h) {
-  hipStream_t q[26] = {h->s_lstm, h->s_ctx, h->s_mix, h->s_up, h->s_fx, h->s_p8, h->late ? h->late->s_bm : nullptr};
+  hipStream_t q[28] = {h->s_lstm, h->s_ctx, h->s_mix, h->s_up, h->s_fx, h->s_p8, h->late ? h->late->s_bm : nullptr};
   int n = 7;
   if (h->p8) n += cmx_p8stage_streams(h->p8, q + n, 24 - n);
   for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_sh[i];   // (null entries are skipped)
   for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_cx[i];
   for (int i = 0; i < 2 && n < 26; ++i) q[n++] = h->s_ls[i];
+  for (int i = 0; i < 2 && n < 28; ++i) q[n++] = h->s_fs[i];
   const int all = cmx_overlap_probe(q, n, &h->probe_n);
   h->probe_all = all < 0 ? 0 : all;
   h->overlap = all < 0 ? -1 : all == h->probe_n ? 1 : 0;
@@ -304,6 +316,7 @@ static hipError_t slot_done(Slot& s) {
   if (e == hipSuccess && s.journalled) e = hipEventSynchronize(s.ev_jr);
   if (e == hipSuccess && s.cxvoted) e = hipEventSynchronize(s.ev_cxvote);
   if (e == hipSuccess && s.lsvoted) e = hipEventSynchronize(s.ev_lsvote);
+  if (e == hipSuccess && s.fsvoted) e = hipEventSynchronize(s.ev_fsvote);
   return e == hipSuccess && s.voted ? hipEventSynchronize(s.ev_vote) : e;
 }
 // the journal's partial records of every finished chunk below `upto`, in stream order (each chunk's copy is waited for: they land in order on s_mix)
@@ -343,6 +356,15 @@ static std::string lstm_vote_text(const unsigned long long r[8]) {
   std::string s = "LSTM shadow vote: the " + std::to_string(r[2]) + " LSTM-stage instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream byte " +
                   std::to_string(r[4]) + ", " + (c < 256 ? "distribution entry " + std::to_string(c) : c < 264 ? "bit " + std::to_string(c - 256) + "'s prediction (layer-0 column 2077)" :
                                                  "bit " + std::to_string(c - 264) + "'s ex") + ": ";
+  if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
+  else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own stage)" : "");
+  return s + " (the stream's output is void)";
+}
+// What an fxcm vote's record (cmx_fxcmvote_report's eight words) says, for an error message
+static std::string fxcm_vote_text(const unsigned long long r[8]) {
+  std::string s = "fxcm shadow vote: the " + std::to_string(r[2]) + " fxcm-stage instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream bit " +
+                  std::to_string(r[4]) + " (byte " + std::to_string(r[4] >> 3) + ", bit " + std::to_string(r[4] & 7) + "), fxcm column " + std::to_string(r[5]) + " (layer-0 column " +
+                  std::to_string(3 + r[5]) + "): ";
   if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
   else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own stage)" : "");
   return s + " (the stream's output is void)";
@@ -484,6 +506,30 @@ static void lstm_shadow_drop(cmx_pipeline* h) {
   h->lstm_shadow = 0;
 }
 
+// everything cmx_pipeline_set_fxcm_shadow and the first begin (or pretrain) behind it made; before the stream's own fxcm handle goes
+static void fxcm_shadow_drop(cmx_pipeline* h) {
+  if (!h->fxcm_shadow) return;
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();
+  cmx_fxcmvote_destroy(h->fsvote); h->fsvote = nullptr;
+  for (int i = 0; i < 2; ++i) {
+    cmx_fxcm_destroy(h->fs[i]); h->fs[i] = nullptr;
+    if (h->s_fs[i]) cmx_destroy_stream(h->s_fs[i]);
+    h->s_fs[i] = nullptr;
+    if (h->d_fs_scratch[i]) (void)hipFree(h->d_fs_scratch[i]);
+    h->d_fs_scratch[i] = nullptr;
+  }
+  for (Slot& s : h->slot) {
+    for (float*& p : s.d_fsp) { if (p) (void)hipFree(p); p = nullptr; }
+    if (s.h_fsvote) (void)hipHostFree(s.h_fsvote);
+    s.h_fsvote = nullptr;
+    for (hipEvent_t* e : {&s.ev_fs[0], &s.ev_fs[1], &s.ev_fsvote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    s.fsvoted = false;
+  }
+  wg_unclaim(h, 4 * h->fxcm_shadow);
+  h->fxcm_shadow = 0;
+}
+
 void cmx_pipeline_destroy(cmx_pipeline_t* h) {
   if (!h) return;
   if (h->late) {
@@ -505,6 +551,7 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
   shadow_drop(h);
   ctx_shadow_drop(h);
   lstm_shadow_drop(h);
+  fxcm_shadow_drop(h);
   wg_release(h);
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
@@ -899,6 +946,75 @@ int cmx_pipeline_debug_lstm_shadow_xor(cmx_pipeline_t* h, int instance, int regi
   if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_lstm_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
   return cmx_lstm_debug_state_xor(x, region, index, xor_mask);
 }
+// ---- shadow fxcm stages and their vote (include/cmix_amd.h; fxcm_vote.hip) ----
+// Reserves here what can be refused -- k streams of the factory (the queue budget) and 4 resident workgroups per shadow --; the k handles (4.4 GB
+// each, no parser), the vote and the per-slot row buffers are made at the first begin or at pretrain, whichever comes first. Refused after
+// cmx_pipeline_pretrain: fxcm IS pretrained (predictor.cpp:471-476) and a shadow made now would have missed the dictionary.
+int cmx_pipeline_set_fxcm_shadow(cmx_pipeline_t* h, int k) {
+  if (!h) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: k must be 0, 1 or 2 shadow fxcm stages (a vote has 2 or 3 instances)"); return 1; }
+  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: only before the first chunk"); return 1; }
+  if (k && !h->fxcm) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: the fxcm stage is not on the device (cmx_pipeline_enable_fxcm first)"); return 1; }
+  if (k && h->pretrained && k != h->fxcm_shadow) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: only before cmx_pipeline_pretrain (fxcm learns the dictionary: a shadow made now would have missed it)"); return 1; }
+  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
+  if (k == h->fxcm_shadow) return 0;
+  fxcm_shadow_drop(h);
+  if (k == 0) return probe_streams(h) < 0 ? 1 : 0;
+  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) {
+    cmx_set_err("cmx_pipeline_set_fxcm_shadow: this process holds " + std::to_string(cmx_hw_queues(h->device)) + " dedicated hardware queues on device " + std::to_string(h->device) +
+                " and " + std::to_string(k) + " shadow fxcm stage(s) need one each, the limit is " + std::to_string(CMX_MAX_HW_QUEUES));
+    return 1;
+  }
+  if (!wg_claim(h, 4 * k, "cmx_pipeline_set_fxcm_shadow")) return 1;
+  h->fxcm_shadow = k;
+  for (int i = 0; i < k; ++i)
+    if (cmx_make_stream(&h->s_fs[i], 0)) { fxcm_shadow_drop(h); return 1; }   // (the factory has said why)
+  return probe_streams(h) < 0 ? 1 : 0;
+}
+// the first begin (or pretrain) with shadow fxcm stages: the handles, the vote, the per-slot buffers, the pretraining scratch
+static int fxcm_shadow_build(cmx_pipeline* h) {
+  const size_t n = h->max_chunk;
+  h->fsvote = cmx_fxcmvote_create(h->device, 1 + h->fxcm_shadow);
+  if (!h->fsvote) return 1;
+  for (int i = 0; i < h->fxcm_shadow; ++i) {
+    h->fs[i] = cmx_fxcm_create_shadow(h->device);
+    if (!h->fs[i]) return 1;
+  }
+  bool ok = hipSetDevice(h->device) == hipSuccess;
+  for (Slot& s : h->slot) {
+    for (int i = 0; i < h->fxcm_shadow; ++i)
+      ok = ok && hipMalloc((void**)&s.d_fsp[i], 8 * n * 434 * sizeof(float)) == hipSuccess && hipEventCreateWithFlags(&s.ev_fs[i], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&s.h_fsvote, 14 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_fsvote, hipEventDisableTiming) == hipSuccess;
+    if (ok) memset(s.h_fsvote, 0, 14 * 8);
+  }
+  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_begin: buffer allocation for the shadow fxcm stages failed"); return 1; }
+  return 0;
+}
+int cmx_pipeline_fxcm_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err("cmx_pipeline_fxcm_shadow_report: bad argument"); return 1; }
+  if (!h->fsvote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
+  return cmx_fxcmvote_report(h->fsvote, out);
+}
+int cmx_pipeline_fxcm_shadow_values(cmx_pipeline_t* h, uint32_t words[3 * CMX_FXCMVOTE_COLS], uint32_t* bit, uint32_t* byte) {
+  if (!h || !words) { cmx_set_err("cmx_pipeline_fxcm_shadow_values: bad argument"); return 1; }
+  if (!h->fsvote) { memset(words, 0, 3 * CMX_FXCMVOTE_COLS * 4); if (bit) *bit = 0; if (byte) *byte = 0; return 0; }
+  return cmx_fxcmvote_values(h->fsvote, words, bit, byte);
+}
+static cmx_fxcm_t* fxcm_shadow_instance(cmx_pipeline* h, int i) { return i == 0 ? h->fxcm : i > 0 && i <= h->fxcm_shadow ? h->fs[i - 1] : nullptr; }
+int cmx_pipeline_fxcm_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[CMX_FXCM_STATE_OUT]) {
+  if (!h || !out) { cmx_set_err("cmx_pipeline_fxcm_shadow_state_diff: bad argument"); return 1; }
+  cmx_fxcm_t *x = fxcm_shadow_instance(h, a), *y = fxcm_shadow_instance(h, b);
+  if (!x || !y) { cmx_set_err("cmx_pipeline_fxcm_shadow_state_diff: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk or pretrain on)"); return 1; }
+  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_fxcm_shadow_state_diff: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
+  return cmx_fxcm_state_diff(x, y, out);
+}
+int cmx_pipeline_debug_fxcm_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t index, uint32_t xor_mask) {
+  if (!h) { cmx_set_err("cmx_pipeline_debug_fxcm_shadow_xor: null handle"); return 1; }
+  cmx_fxcm_t* x = fxcm_shadow_instance(h, instance);
+  if (!x) { cmx_set_err("cmx_pipeline_debug_fxcm_shadow_xor: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk or pretrain on)"); return 1; }
+  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_fxcm_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
+  return cmx_fxcm_debug_state_xor(x, region, index, xor_mask);
+}
 // 0 strict, 1 tolerance: not strict as soon as EITHER the mixing network or the LSTM computes in its tolerance form
 int cmx_pipeline_stage_overlap(cmx_pipeline_t* h) { return h ? h->overlap : -1; }
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t* h) { return !h ? -1 : (h->lstm_tolerance ? 1 : cmx_mixnet_mode(h->mix)); }
@@ -1035,6 +1151,28 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
     if (cmx_fxcm_run(h->fxcm, bytes, s.d_bytes, n, s.d_fx_pr, s.d_fx_ex, d_layer0, CMX_N_INPUTS, h->s_fx)) return 1;
     (void)hipMemcpyAsync(&s.h_fail[1], cmx_fxcm_fail_flag(h->fxcm), 4, hipMemcpyDeviceToHost, h->s_fx);
     (void)hipEventRecord(s.ev_fx1, h->s_fx);
+    if (h->fxcm_shadow) {   // ---- the same records, bytes and hints on every shadow fxcm stage, into rows of its own; then the vote on the last shadow's stream ----
+      if (!h->fsvote && fxcm_shadow_build(h)) return 1;   // (nothing downstream of the stream's own stage waits for any of this)
+      const int k = h->fxcm_shadow;
+      const float* vr[3] = {d_layer0 + 3, nullptr, nullptr};
+      const size_t stride[3] = {CMX_N_INPUTS, 434, 434};
+      for (int i = 0; i < k; ++i) {
+        hipStream_t q = h->s_fs[i];
+        (void)hipStreamWaitEvent(q, s.ev_fxin, 0);   // the hints (behind the bytes' upload); cmx_fxcm_run_shared adds the wait for the records' upload
+        if (cmx_fxcm_run_shared(h->fs[i], h->fxcm, s.d_bytes, n, s.d_fx_pr, s.d_fx_ex, s.d_fsp[i], 434, q)) return 1;
+        (void)hipMemcpyAsync((unsigned*)(s.h_fsvote + 12) + i, cmx_fxcm_fail_flag(h->fs[i]), 4, hipMemcpyDeviceToHost, q);
+        (void)hipEventRecord(s.ev_fs[i], q);
+        vr[i + 1] = s.d_fsp[i] + 3;
+      }
+      hipStream_t q = h->s_fs[k - 1];
+      (void)hipStreamWaitEvent(q, s.ev_fx1, 0);
+      for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_fs[i], 0);
+      if (cmx_fxcmvote_run(h->fsvote, vr, stride, T, h->fsvote_bits, s.d_bytes, q)) return 1;
+      (void)hipMemcpyAsync(s.h_fsvote, cmx_fxcmvote_record(h->fsvote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
+      (void)hipEventRecord(s.ev_fsvote, q);
+      s.fsvoted = true;
+      h->fsvote_bits += T;
+    }
   }
   lap(3);
   if (h->p8) {  // ---- paq8 stage: front end on this thread, role kernels on its own streams; needs nothing from the other stages ----
@@ -1222,14 +1360,28 @@ int cmx_pipeline_pretrain(cmx_pipeline_t* h, const uint8_t* bytes, size_t n) {
     ok = ok && hipMemsetAsync(zpr, 0, 8 * C * 2, h->s_fx) == hipSuccess && hipMemsetAsync(zex, 0, 8 * C, h->s_fx) == hipSuccess;
     ok = ok && hipStreamWaitEvent(h->s_fx, ev_d, 0) == hipSuccess;
   }
+  // every shadow fxcm stage learns the dictionary too: each chunk on the shared records with the same zero hints, on its own stream into a scratch of
+  // its own; the rows are discarded, nothing is voted
+  hipEvent_t ev_z = nullptr;
+  if (ok && h->fxcm && h->fxcm_shadow) {
+    if (!h->fsvote) ok = fxcm_shadow_build(h) == 0;
+    ok = ok && hipEventCreateWithFlags(&ev_z, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev_z, h->s_fx) == hipSuccess;   // behind the hints' memsets and ev_d
+    for (int i = 0; ok && i < h->fxcm_shadow; ++i) {
+      if (!h->d_fs_scratch[i]) ok = hipMalloc((void**)&h->d_fs_scratch[i], 8 * C * 434 * sizeof(float)) == hipSuccess;
+      ok = ok && hipStreamWaitEvent(h->s_fs[i], ev_z, 0) == hipSuccess;
+    }
+  }
   for (size_t off = 0; ok && off < n; off += C) {
     const size_t m = n - off < C ? n - off : C;
     if (h->fxcm) ok = cmx_fxcm_run(h->fxcm, bytes + off, d + off, m, zpr, zex, h->d_fx_scratch, 434, h->s_fx) == 0;
+    for (int i = 0; ok && h->fxcm && i < h->fxcm_shadow; ++i) ok = cmx_fxcm_run_shared(h->fs[i], h->fxcm, d + off, m, zpr, zex, h->d_fs_scratch[i], 434, h->s_fs[i]) == 0;
     if (ok && h->p8) ok = cmx_p8stage_run(h->p8, bytes + off, m, h->d_p8_scratch, 1591, h->s_p8) == 0;
   }
   ok = hipStreamSynchronize(h->s_ctx) == hipSuccess && ok;
   for (hipStream_t q : h->s_cx) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (h->fxcm) ok = hipStreamSynchronize(h->s_fx) == hipSuccess && ok;
+  for (hipStream_t q : h->s_fs) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
+  if (ev_z) (void)hipEventDestroy(ev_z);
   if (h->p8) ok = hipStreamSynchronize(h->s_p8) == hipSuccess && ok;
   h->pretrained = true;
   if (zpr) (void)hipFree(zpr);
@@ -1433,6 +1585,20 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
     h->failed = true;
     return 1;
   }
+  if (s.fsvoted) {
+    const unsigned* fsfail = (const unsigned*)(s.h_fsvote + 12);
+    if (fsfail[0] || fsfail[1]) {
+      cmx_set_err("cmx_pipeline_wait: an in-launch hand-off of the fxcm kernel of shadow instance " + std::to_string(fsfail[0] ? 1 : 2) +
+                  " timed out (workgroups not co-resident?): the fxcm vote is void from chunk " + std::to_string(index) + " on");
+      h->failed = true;
+      return 1;
+    }
+    if (s.h_fsvote[3]) {   // the fxcm-stage instances disagreed in this chunk or an earlier one (the record is sticky): no repair, the stream stops
+      cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + fxcm_vote_text(s.h_fsvote));
+      h->failed = true;
+      return 1;
+    }
+  }
   if (s.voted) {
     const unsigned* shfail = (const unsigned*)(s.h_vote + 12);
     if (shfail[0] || shfail[1]) {
@@ -1478,6 +1644,7 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
   for (hipStream_t q : h->s_sh) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   for (hipStream_t q : h->s_cx) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   for (hipStream_t q : h->s_ls) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
+  for (hipStream_t q : h->s_fs) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (!ok) { cmx_set_err("cmx_pipeline_sync: device error"); h->failed = true; return 1; }
   if (cmx_ctxmodels_sync(h->ctx) || cmx_mixnet_sync(h->mix)) { h->failed = true; return 1; }
   for (cmx_ctxmodels_t* c : h->cx) if (c && cmx_ctxmodels_sync(c)) { h->failed = true; return 1; }
@@ -1495,6 +1662,16 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
     uint64_t r[8];
     if (cmx_lstmvote_report(h->lsvote, r)) { h->failed = true; return 1; }
     if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + lstm_vote_text(t)); h->failed = true; return 1; }
+  }
+  for (int i = 0; i < 2; ++i)
+    if (h->fs[i] && cmx_fxcm_failed(h->fs[i])) {
+      cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the fxcm kernel of shadow instance " + std::to_string(i + 1) + " timed out (workgroups not co-resident?): the fxcm vote is void");
+      h->failed = true; return 1;
+    }
+  if (h->fsvote) {
+    uint64_t r[8];
+    if (cmx_fxcmvote_report(h->fsvote, r)) { h->failed = true; return 1; }
+    if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + fxcm_vote_text(t)); h->failed = true; return 1; }
   }
   for (cmx_mixnet_t* m : h->sh) if (m && cmx_mixnet_sync(m)) { h->failed = true; return 1; }
   if (h->vote) {
@@ -1601,6 +1778,7 @@ int cmx_pipeline_late_start(cmx_pipeline_t* h, int last_bit) {
   if (hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_pipeline_late_start: device error"); return 1; }   // pretraining is complete
   ctx_shadow_drop(h);
   lstm_shadow_drop(h);
+  fxcm_shadow_drop(h);
   shadow_drop(h);   // a decoder is not covered by the vote (include/cmix_amd.h): it holds no stream, workgroup or buffer of it
   Late* L = new Late();
   h->late = L;

@@ -59,6 +59,29 @@ def lib():
         L.cmx_fxcm_debug_jitter_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_fxcm_debug_ring_waits.argtypes = [C.c_void_p]
         L.cmx_fxcm_debug_slot_parallel.argtypes = [C.c_void_p]
+        L.cmx_fxcm_create_shadow.restype = C.c_void_p
+        L.cmx_fxcm_create_shadow.argtypes = [C.c_int]
+        L.cmx_fxcm_run_shared.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.cmx_fxcm_state_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_fxcm_debug_state_xor.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32]
+        L.cmx_fxcm_debug_layout.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_fxcm_debug_state_read.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.cmx_fxcmvote_create.restype = C.c_void_p
+        L.cmx_fxcmvote_create.argtypes = [C.c_int, C.c_int]
+        L.cmx_fxcmvote_destroy.argtypes = [C.c_void_p]
+        L.cmx_fxcmvote_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.cmx_fxcmvote_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_fxcmvote_record.restype = C.c_void_p
+        L.cmx_fxcmvote_record.argtypes = [C.c_void_p]
+        L.cmx_fxcmvote_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_fxcmvote_last.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_set_fxcm_shadow.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_pipeline_fxcm_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_fxcm_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_fxcm_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.cmx_pipeline_debug_fxcm_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32]
+        L.cmx_set_fxcm_shadow.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_fxcm_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_mixnet_create.restype = C.c_void_p
         L.cmx_mixnet_create.argtypes = [C.c_int]
         L.cmx_mixnet_destroy.argtypes = [C.c_void_p]
@@ -588,6 +611,99 @@ class LstmVote:
     def close(self):
         if getattr(self, "h", None):
             lib().cmx_lstmvote_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# the redundant fxcm-stage vote (include/cmix_amd.h, cmx_fxcmvote_*; the rule's specification is cmix_amd.fxcmvote.fxcm_vote_reference)
+FXCM_STATE_REGIONS = ("const_tables", "map_buckets", "map_statemaps", "sscm", "sm1_t", "rcm_t", "mhash", "sp_table", "buffer", "wx", "apm", "fxdev")
+FXCMVOTE_COLS = 431   # CMX_FXCMVOTE_COLS: FXCM::Predict()'s values of one bit = layer-0 columns 3..433
+# the arrays of cmx_fxcm_state_diff in their fixed order (src/fxcm_build.h's blocks, region by region)
+FXCM_STATE_ARRAYS = tuple(["squash", "stretch", "wrt"] + ["sta[%d]" % i for i in range(6)] + ["maps[%d].tab" % k for k in range(31)] + ["apm_pattern[%d]" % j for j in range(6)] +
+                          ["maps[%d].t" % k for k in range(31)] + ["maps[%d].sm" % k for k in range(31)] + ["sscm_data[%d]" % j for j in range(7)] +
+                          ["sm1_t[%d]" % j for j in range(3)] + ["rcm_t", "mhash", "sp_table", "buffer"] + ["wx[%d]" % k for k in range(12)] +
+                          ["apm_t[%d]" % j for j in range(6)] + ["FxDev"])
+
+
+def _fxcm_region(r):
+    return FXCM_STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
+
+
+def _fxcm_vote_values(fn, h, n):
+    words, bit, byte = np.zeros(3 * FXCMVOTE_COLS, np.uint32), C.c_uint32(0), C.c_uint32(0)
+    if fn(h, words.ctypes.data, C.byref(bit), C.byref(byte)):
+        raise CmxError(last_error())
+    return {"words": words[:FXCMVOTE_COLS * n].reshape(n, FXCMVOTE_COLS).copy(), "bit": int(bit.value), "byte": int(byte.value)}
+
+
+def _fxcm_state_diff(out):
+    v = [int(x) for x in out]
+    first = {"region": v[1], "index": v[2], "a": v[3], "b": v[4]} if v[0] else None
+    return {"words": v[0], "first": first, "per_region": dict(zip(FXCM_STATE_REGIONS, v[5:17])), "raw": v}
+
+
+def fxcm_layout(fx):
+    """the state arrays of an Fxcm handle in cmx_fxcm_state_diff's order (cmx_fxcm_debug_layout): list of dicts name, region (its name), offset (words
+    inside the region), words; the last one is FxDev itself"""
+    out = (C.c_uint64 * (3 * len(FXCM_STATE_ARRAYS)))()
+    n = lib().cmx_fxcm_debug_layout(fx.h, out)
+    if n != len(FXCM_STATE_ARRAYS):
+        raise CmxError(last_error() if n < 0 else "cmx_fxcm_debug_layout: %d arrays, expected %d" % (n, len(FXCM_STATE_ARRAYS)))
+    return [{"name": FXCM_STATE_ARRAYS[i], "region": FXCM_STATE_REGIONS[int(out[3 * i])], "offset": int(out[3 * i + 1]), "words": int(out[3 * i + 2])} for i in range(n)]
+
+
+class FxcmVote:
+    """The fxcm-stage vote kernel over n = 2 or 3 instances' rows (CUDA float32 / 4-byte-word tensors [T, stride]): a [T, 2078] layer-0 matrix is read in
+    place from its columns 3..433, a [T, 434] matrix (what Fxcm.run_shared writes) from columns 3..433 as well, a [T, 431] matrix as it is. The record is
+    sticky across run()."""
+
+    def __init__(self, n, device=0):
+        self.n = int(n)
+        self.h = lib().cmx_fxcmvote_create(device, self.n)
+        if not self.h:
+            raise CmxError(last_error())
+
+    def run(self, rows, stream_bit0=0, data=None, stream=None):
+        import torch
+        assert len(rows) == self.n
+        T = int(rows[0].shape[0])
+        ptr, stride = [], []
+        for r in rows:
+            assert r.is_cuda and r.is_contiguous() and r.element_size() == 4 and r.dim() == 2 and r.shape[0] == T and r.shape[1] >= FXCMVOTE_COLS
+            ptr.append(r.data_ptr() + (0 if r.shape[1] == FXCMVOTE_COLS else 12))
+            stride.append(int(r.shape[1]))
+        if stream is None:
+            stream = torch.cuda.current_stream(rows[0].device).cuda_stream
+        ap = (C.c_void_p * 3)(*ptr)
+        ast = (C.c_size_t * 3)(*stride)
+        if lib().cmx_fxcmvote_run(self.h, ap, ast, T, int(stream_bit0), data.data_ptr() if data is not None else None, C.c_void_p(stream)):
+            raise CmxError(last_error())
+
+    def report(self):
+        """as Vote.report: bits voted, first_bit = the first event's stream bit, column = the fxcm column c (layer-0 column 3 + c). Synchronises."""
+        return _vote_report(lib().cmx_fxcmvote_report, self.h)
+
+    def last(self):
+        """as Vote.last"""
+        out = (C.c_uint64 * 4)()
+        if lib().cmx_fxcmvote_last(self.h, out):
+            raise CmxError(last_error())
+        v = [int(x) for x in out]
+        ev = v[0] != 0
+        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
+
+    def values(self):
+        """the captured row of the first event: words [n, 431] u32, the bit coded there and its byte"""
+        return _fxcm_vote_values(lib().cmx_fxcmvote_values, self.h, self.n)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().cmx_fxcmvote_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -1270,6 +1386,33 @@ class Pipeline:
         if lib().cmx_pipeline_debug_lstm_shadow_xor(self.h, int(instance), _lstm_region(region), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
+    def set_fxcm_shadow(self, k):
+        """k = 0 / 1 / 2 shadow fxcm stages voting on every chunk's 431 columns (include/cmix_amd.h): after enable_fxcm, before the first chunk and
+        before pretrain (fxcm learns the dictionary); wait / fetch / sync then fail the chunk in which the instances disagree."""
+        if lib().cmx_pipeline_set_fxcm_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+        self._fxcm_shadow = int(k)
+
+    def fxcm_shadow_report(self):
+        """as FxcmVote.report (all zero while nothing was voted)"""
+        return _vote_report(lib().cmx_pipeline_fxcm_shadow_report, self.h)
+
+    def fxcm_shadow_values(self):
+        """as FxcmVote.values"""
+        return _fxcm_vote_values(lib().cmx_pipeline_fxcm_shadow_values, self.h, 1 + getattr(self, "_fxcm_shadow", 0))
+
+    def fxcm_shadow_state_diff(self, a, b):
+        """Fxcm.state_diff of instances a and b (0 = the stream's own stage, 1.. = the shadows), between chunks"""
+        out = (C.c_uint64 * 17)()
+        if lib().cmx_pipeline_fxcm_shadow_state_diff(self.h, int(a), int(b), out):
+            raise CmxError(last_error())
+        return _fxcm_state_diff(out)
+
+    def debug_fxcm_shadow_xor(self, instance, region, index, xor_mask):
+        """Test hook: Fxcm.debug_state_xor on one instance, between chunks."""
+        if lib().cmx_pipeline_debug_fxcm_shadow_xor(self.h, int(instance), _fxcm_region(region), int(index), int(xor_mask)):
+            raise CmxError(last_error())
+
     def mixnet_mode(self):
         """0 strict (bit-exact, the default), 1 tolerance -- as the library reports it"""
         return lib().cmx_pipeline_mixnet_mode(self.h)
@@ -1560,6 +1703,15 @@ class Predictor:
         """as LstmVote.report (all zero unless the handle compresses)"""
         return _vote_report(lib().cmx_lstm_shadow_report, self.h)
 
+    def set_fxcm_shadow(self, k):
+        """Shadow fxcm stages of the look-ahead pipeline (include/cmix_amd.h, cmx_set_fxcm_shadow): before the first stage_input / Predict."""
+        if lib().cmx_set_fxcm_shadow(self.h, int(k)):
+            raise CmxError(last_error())
+
+    def fxcm_shadow_report(self):
+        """as FxcmVote.report (all zero unless the handle compresses)"""
+        return _vote_report(lib().cmx_fxcm_shadow_report, self.h)
+
     def debug_ctx_shadow_xor(self, after_chunk, instance, region, lane, index, xor_mask):
         """Test hook: one Pipeline.debug_ctx_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""
         if lib().cmx_debug_ctx_shadow_xor(self.h, int(after_chunk), int(instance), _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
@@ -1617,11 +1769,56 @@ class Fxcm:
     """The fxcm stage of one stream on one GPU (chunk mode): layer-0 columns 3..433. The text parser half runs on the
     calling thread inside run(); the learned tables live on the device (include/cmix_amd.h section 2f)."""
 
-    def __init__(self, dictionary_path=None, device=0):
-        self.h = lib().cmx_fxcm_create(dictionary_path.encode() if isinstance(dictionary_path, str) else dictionary_path, device)
+    def __init__(self, dictionary_path=None, device=0, shadow=False):
+        """shadow=True: a shadow instance (cmx_fxcm_create_shadow) -- the same device state, no parser and no dictionary; run_shared() only"""
+        self.shadow = bool(shadow)
+        if self.shadow:
+            self.h = lib().cmx_fxcm_create_shadow(device)
+        else:
+            self.h = lib().cmx_fxcm_create(dictionary_path.encode() if isinstance(dictionary_path, str) else dictionary_path, device)
         if not self.h:
             raise CmxError(last_error())
         self._keep = []
+        self._last = None   # (d_bytes, lstmpr, lstmex) of the most recent run(): what a shadow's run_shared reads beside the records
+
+    def run_shared(self, owner, probs=None, stream=None):
+        """A shadow's launch on the records, bytes and hints of owner's most recent run() (cmx_fxcm_run_shared): writes columns 3..433 of
+        probs [8N, >=434] f32 (default: a dense [8N, 434] buffer of 0.5)."""
+        import torch
+        if owner._last is None:
+            raise CmxError("Fxcm.run_shared: the owner has not run a chunk")
+        d_bytes, lstmpr, lstmex = owner._last
+        N = int(d_bytes.numel())
+        dev = lstmpr.device
+        if probs is None:
+            probs = torch.full((8 * N, 434), 0.5, dtype=torch.float32, device=dev)
+        assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.shape[0] == 8 * N and probs.shape[1] >= 434
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        if lib().cmx_fxcm_run_shared(self.h, owner.h, d_bytes.data_ptr(), N, lstmpr.data_ptr(), lstmex.data_ptr(), probs.data_ptr(), probs.shape[1], C.c_void_p(stream)):
+            raise CmxError(last_error())
+        self._keep.append((d_bytes, lstmpr, lstmex))
+        return probs
+
+    def state_diff(self, other):
+        """Every word of this handle's and `other`'s state in HBM compared (include/cmix_amd.h, cmx_fxcm_state_diff): dict words, first (region, index,
+        a, b), per_region, raw. Raises when the byte counts differ. Synchronises the device."""
+        out = (C.c_uint64 * 17)()
+        if lib().cmx_fxcm_state_diff(self.h, other.h, out):
+            raise CmxError(last_error())
+        return _fxcm_state_diff(out)
+
+    def debug_state_read(self, region, index, count):
+        """Test readout: `count` words of a region from `index` on, as uint32 (cmx_fxcm_debug_state_read). Synchronises."""
+        out = np.zeros(int(count), np.uint32)
+        if lib().cmx_fxcm_debug_state_read(self.h, _fxcm_region(region), int(index), int(count), out.ctypes.data):
+            raise CmxError(last_error())
+        return out
+
+    def debug_state_xor(self, region, index, xor_mask):
+        """Test hook: XOR one state word (region: number or FXCM_STATE_REGIONS name) between launches; regions whose words address memory are refused."""
+        if lib().cmx_fxcm_debug_state_xor(self.h, _fxcm_region(region), int(index), int(xor_mask)):
+            raise CmxError(last_error())
 
     def close(self):
         if getattr(self, "h", None):
@@ -1678,6 +1875,7 @@ class Fxcm:
         if rc:
             raise CmxError(last_error())
         self._keep.append(d_bytes)   # the kernel reads it asynchronously: every launch's copy lives until sync() / close()
+        self._last = (d_bytes, lstmpr, lstmex)
         return probs
 
     def sync(self):

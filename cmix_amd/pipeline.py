@@ -59,7 +59,7 @@ class EngineStream:
     is for a compressor (reference src/predictor.cpp:361-469), a sub-chunk of known bytes at a time. feed() enqueues;
     finish() returns the container bytes (header + arithmetic code), identical to the reference binary's file."""
 
-    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0, repair=0, ctx_shadow=0, journal=0, lstm_shadow=0):
+    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0, repair=0, ctx_shadow=0, journal=0, lstm_shadow=0, fxcm_shadow=0):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", device_index)
@@ -89,6 +89,8 @@ class EngineStream:
             self.pipe.set_ctx_shadow(ctx_shadow)
         if lstm_shadow:   # that many shadow LSTM stages vote on every sub-chunk's distributions, bit predictions and ex (cmx_pipeline_set_lstm_shadow): finish() raises on a disagreement
             self.pipe.set_lstm_shadow(lstm_shadow)
+        if fxcm_shadow:   # that many shadow fxcm stages vote on every sub-chunk's 431 columns (cmx_pipeline_set_fxcm_shadow): finish() raises on a disagreement
+            self.pipe.set_fxcm_shadow(fxcm_shadow)
         if journal:   # per-block digests of every sub-chunk's rows, selectors, bits and p, blocks of 2^journal bits (cmx_pipeline_set_journal): journal()
             self.pipe.set_journal(19 if journal is True else int(journal))
         self.waited = 0

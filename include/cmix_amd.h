@@ -132,6 +132,11 @@ int cmx_debug_ctx_shadow_xor(cmx_t*, uint64_t after_chunk, int instance, int reg
  * cmx_lstmvote_report. */
 int cmx_set_lstm_shadow(cmx_t*, int k);
 int cmx_lstm_shadow_report(cmx_t*, uint64_t out[8]);
+/* Shadow fxcm stages of the look-ahead pipeline (cmx_pipeline_set_fxcm_shadow, k = 0 / 1 / 2): before the first cmx_stage_input or cmx_predict; they
+ * are set before the dictionary is pretrained, so every instance learns it. A disagreement fails the call that waits for that chunk. The programs in
+ * integration/ read CMIX_FXCM_SHADOW=1|2; the library reads no environment variable for it. cmx_fxcm_shadow_report: as cmx_fxcmvote_report. */
+int cmx_set_fxcm_shadow(cmx_t*, int k);
+int cmx_fxcm_shadow_report(cmx_t*, uint64_t out[8]);
 /* The stream journal of a cmx_t (section "Stream journal" below has the digest; log2_block_bits 0 = off, else 6..19, 19 = the reference trace's 64 KB;
  * before the first cmx_stage_input / cmx_predict). A COMPRESSOR's handle (look-ahead mode) journals every chunk on the device
  * (cmx_pipeline_set_journal: all 179 words per block; coexists with verify, the shadows and repair). A DECODER's handle (late-bit mode)
@@ -537,6 +542,76 @@ int cmx_fxcm_debug_jitter_counts(cmx_fxcm_t*, unsigned out18[18]);
  * flight and waited for it; the model's slot_parallel word as the kernels read it from device memory (0 under CMX_FXCM_SERIAL_MAPS=1; syncs). -1: error. */
 int cmx_fxcm_debug_ring_waits(cmx_fxcm_t*);
 int cmx_fxcm_debug_slot_parallel(cmx_fxcm_t*);
+/* SHADOW INSTANCES (for the vote below). ONE PARSER, SHARED RECORDS: the host text parser runs once per chunk, in the stream's own handle (the OWNER,
+ * cmx_fxcm_create). cmx_fxcm_create_shadow makes a handle with the same device state (the same fxb::build, which reads no dictionary) and NO parser;
+ * cmx_fxcm_run and the decoder's calls refuse it. cmx_fxcm_run_shared(shadow, owner, ...) launches the unchanged roles kernel on the shadow's own
+ * FxDev, row buffer, hand-off block and fail flag, reading the records the owner's MOST RECENT cmx_fxcm_run uploaded: `stream` waits for that staging
+ * slot's upload event, nbytes must be that chunk's size, and a shadow must have run exactly the chunks its owner ran before this one (refused with the
+ * two byte counts otherwise). d_bytes, d_lstmpr, d_lstmex: as cmx_fxcm_run, normally the owner's own arrays; d_probs: the shadow's rows (columns
+ * 3..433 of pstride >= 434). An owner takes at most two shadows. The parser's records, the chunk's bytes and the LSTM hints exist once and are read by
+ * every instance: they are NOT covered by the vote. STAGING RING: the owner refills a staging slot only when its own launch on it AND every shadow
+ * launch that read it have completed (a per-reader event in the owner's slot, waited for where the owner's own is); cmx_fxcm_debug_ring_waits counts a
+ * launch that met any of them in flight, once. Destroy in any order. Under CMX_FXCM_JITTER a shadow stalls with a seed of its own. */
+cmx_fxcm_t* cmx_fxcm_create_shadow(int device);
+int cmx_fxcm_run_shared(cmx_fxcm_t* shadow, cmx_fxcm_t* owner, const uint8_t* d_bytes, size_t nbytes, const int16_t* d_lstmpr, const uint8_t* d_lstmex,
+                        float* d_probs, size_t pstride, void* stream);
+/* THE REDUNDANT FXCM-STAGE VOTE (opt-in; src/fxcm_vote.hip). n = 2 or 3 instances of the unchanged roles kernel (above) and a word-for-word
+ * comparison of what they wrote. A chunk of nbits bits (whole bytes) has nbits rows; a row is one BIT: the 431 values FXCM::Predict() returns before
+ * that bit is coded, compared as 32-bit WORDS, never as floats. Row t of instance i is at d_rows[i] + t * pstride[i]: instance 0 is the stream's own
+ * stage, read IN PLACE from the slot's layer-0 rows (d_rows[0] = layer0 + 3, pstride 2078; such a row's base is only 4-byte aligned, differently from
+ * row to row, so the kernel uses 4-byte loads and nothing wider); a shadow's dense buffer is d_probs + 3 with pstride 434. Elements are ordered by
+ * e = t * 431 + c, c = 0..430 = layer-0 column 3 + c. The rule is cmx_vote_run's: n = 3: all equal agree, exactly two equal make the third the ODD
+ * instance, all different is NO MAJORITY; n = 2: different is no majority. Asynchronous on `stream`: one kernel with one wavefront per row (grid-stride;
+ * a per-lane minimum key (e << 2 | odd), count and odd mask, one reduction and one atomic each of the three per wave that saw a difference; no LDS, no scratch) and a
+ * one-wave kernel behind it that folds the chunk into the sticky DEVICE record. d_bytes ([nbits / 8], may be NULL: captured as 0): the chunk's bytes.
+ * _report / _record / _last: the eight / four words of cmx_lstmvote_report / _record / _last with BITS where those have bytes: [0] chunks voted,
+ * [1] bits voted, [2] n, [3] chunks with an event, then of the FIRST event [4] (of _last: [1]) its stream bit, [5] (of _last: [2]) its column c,
+ * [6] (of _last: [3]) the odd instance or UINT64_MAX = no majority, [7] (of _last: [0]) the chunk's differing elements; "first" = lowest bit, then
+ * lowest column. _values: the capture of the first event's row -- words[i * 431 + c] of instance i (n x 431 used), the bit coded at that row and its
+ * byte. Synchronises. NO REPAIR: the mixing network has consumed the columns when the host sees a vote; an event stops the stream. */
+#define CMX_FXCMVOTE_COLS 431
+typedef struct cmx_fxcmvote cmx_fxcmvote_t;
+cmx_fxcmvote_t* cmx_fxcmvote_create(int device, int n);
+void cmx_fxcmvote_destroy(cmx_fxcmvote_t*);
+int cmx_fxcmvote_run(cmx_fxcmvote_t*, const float* const* d_rows, const size_t* pstride, size_t nbits, uint64_t stream_bit0, const uint8_t* d_bytes, void* stream);
+int cmx_fxcmvote_report(cmx_fxcmvote_t*, uint64_t out[8]);
+const unsigned long long* cmx_fxcmvote_record(cmx_fxcmvote_t*);
+int cmx_fxcmvote_values(cmx_fxcmvote_t*, uint32_t words[3 * CMX_FXCMVOTE_COLS], uint32_t* bit, uint32_t* byte);
+int cmx_fxcmvote_last(cmx_fxcmvote_t*, uint64_t out[4]);
+/* Every 32-bit word of two handles' state in HBM, compared (both on one device; a == b is refused; synchronises; 4.4 GB per handle: after an event
+ * and in tests, between chunks only). The arrays are the blocks fxb::build (src/fxcm_build.h) asks for, which two handles allocate in the same order
+ * and size; an index is a word offset into the region's arrays laid end to end, each array rounded up to whole words:
+ *    0 constant tables  squash, stretch, wrt, the six state tables, the 31 maps' lookup tables `tab` (map order), the six 33-entry APM fill patterns
+ *    1 map buckets      maps[k].t, k = 0..30
+ *    2 map StateMaps    maps[k].sm, k = 0..30 ([C_k][256])
+ *    3 SSCM tables      sscm_data[0..6]
+ *    4 sm1_t            sm1_t[0..2]
+ *    5 rcm_t            6 mhash            7 sp_table            8 buffer (the byte history)
+ *    9 wx               wx[0..11]: the ten first-layer mixers' rows of 512 weights, the two final mixers' rows of 16
+ *   10 APM tables       apm_t[0..5]
+ *   11 FxDev            the stream's FxDev itself (src/fxcm_dev.h) as sizeof(FxDev) / 4 words with every device pointer (and the padding of the four
+ *                       match candidates) read as 0: the per-map cp / cp0 / runp / cxt / sm_cxt, the SSCM, sm1, run-map, match and sparse-match
+ *                       scalars, pos, and everything from mx_elim to rec; an index is the word's offset in FxDev
+ * NOT compared: the device pointers inside FxDev (they differ by construction), the per-launch hand-off block and row buffer (rewritten by every
+ * launch before they are read), the staged records (the owner's only). The host-side counter bytes_done is compared first: a difference there is an
+ * ERROR return whose message says so. out[0] differing words; [1..4] the first difference in region-then-array-then-address order: region, index, the
+ * word of a, the word of b (UINT64_MAX without a difference); [5..16] the count per region. */
+#define CMX_FXCM_STATE_REGIONS 12
+#define CMX_FXCM_STATE_ARRAYS 141
+#define CMX_FXCM_STATE_OUT 17
+int cmx_fxcm_state_diff(cmx_fxcm_t* a, cmx_fxcm_t* b, uint64_t out[CMX_FXCM_STATE_OUT]);
+/* TEST HOOK: XOR one state word (addressed as cmx_fxcm_state_diff reports it) between launches. Synchronises the device. A data change only: no kernel
+ * stops, addresses memory with the changed word, or times out. OPEN: regions 2 (map StateMaps), 3 (SSCM), 4 (sm1_t), 5 (rcm_t), 9 (wx), 10 (APM):
+ * every use of such a word is arithmetic or an index shifted into the range of the table it meets. REFUSED with a message: 0 (table values index other
+ * tables), 1 (map buckets: the probe and replacement walks were not followed to the end), 6, 7, 8 (history positions and bytes the match models follow
+ * in loops), 11 (offsets and indices). The reasoning per region stands next to the hook in src/fxcm_vote.hip. */
+int cmx_fxcm_debug_state_xor(cmx_fxcm_t*, int region, uint64_t index, uint32_t xor_mask);
+/* TEST READOUT: per array, in the order above, [3 i] its region, [3 i + 1] its word offset inside the region, [3 i + 2] its words; the last entry is
+ * FxDev. Returns the number of arrays (CMX_FXCM_STATE_ARRAYS) or -1. Synchronises. */
+int cmx_fxcm_debug_layout(cmx_fxcm_t*, uint64_t out[3 * CMX_FXCM_STATE_ARRAYS]);
+/* TEST READOUT: `count` words of a region from `index` on (addressed as above; every region, 11 with its pointers read as 0) into out. Synchronises. A
+ * test takes two readouts around a launch to learn which words the launch trained, i.e. which words the next one will read. */
+int cmx_fxcm_debug_state_read(cmx_fxcm_t*, int region, uint64_t index, uint64_t count, uint32_t* out);
 
 /* ---- callers of the path: arithmetic coder + container header (HOST code) -------------------------------------
  * Replaces Encoder::Encode/Flush (src/coder/encoder.cpp:10-39), Decoder::Decoder/Decode (src/coder/decoder.cpp:3-39)
@@ -776,6 +851,31 @@ int cmx_pipeline_lstm_shadow_report(cmx_pipeline_t*, uint64_t out[8]);
 int cmx_pipeline_lstm_shadow_values(cmx_pipeline_t*, uint32_t words[3 * CMX_LSTMVOTE_COLS], uint32_t* byte);
 int cmx_pipeline_lstm_shadow_state_diff(cmx_pipeline_t*, int a, int b, uint64_t out[16]);
 int cmx_pipeline_debug_lstm_shadow_xor(cmx_pipeline_t*, int instance, int region, uint64_t index, uint32_t xor_mask);
+/* SHADOW FXCM STAGES (opt-in, k = 0 off / 1 / 2; needs cmx_pipeline_enable_fxcm; before the first chunk AND before cmx_pipeline_pretrain: unlike the
+ * LSTM, fxcm is pretrained, predictor.cpp:471-476, and a shadow set afterwards would have missed the dictionary -- refused): k shadow handles
+ * (cmx_fxcm_create_shadow: 4.4 GB of tables each, no parser) run the unchanged roles kernel again on every chunk, each on a stream of its own, on the
+ * records the stream's own parser produced for that chunk (cmx_fxcm_run_shared), the slot's bytes and the slot's LSTM hints, behind the hints' event and
+ * the records' upload, into rows of its own (8 max_chunk x 434 floats per slot and shadow). A vote (cmx_fxcmvote_*; instance 0 = the stream's own
+ * stage, read in place from columns 3..433 of the slot's layer-0 rows) follows every chunk on the last shadow's stream. The records, the bytes and the
+ * hints are shared by all instances and NOT covered. Nothing downstream -- the mixing network -- waits for a shadow or for the vote; a slot is not
+ * reused, and cmx_pipeline_wait does not return, before the slot's vote has read the in-place rows. cmx_pipeline_pretrain runs every dictionary chunk
+ * on every shadow as well (shared records, the zero hints, a scratch and stream of its own; rows discarded, no vote). Reserved at the set call, refused
+ * with the reason: k streams of the queue budget (CMX_MAX_HW_QUEUES) and 4 resident workgroups per shadow. The handles, the vote and the buffers are
+ * created at the first cmx_pipeline_begin or at cmx_pipeline_pretrain, whichever comes first; k = 0 gives everything back, and with k = 0 nothing is
+ * allocated, launched or waited for. fxcm has no tolerance form, so the switch does not matter here. cmx_pipeline_wait / _fetch / _sync fail the chunk
+ * in which the instances first disagreed -- the message names the chunk, the stream bit (and byte + bit in byte), "fxcm column c (layer-0 column
+ * 3 + c)", and the odd instance ("the stream's own stage" for 0) or "no majority between 2 instances" -- and void the handle, which can still be
+ * diagnosed (_fxcm_shadow_report / _values: as cmx_fxcmvote_report / _values, all zero while nothing was voted; _fxcm_shadow_state_diff:
+ * cmx_fxcm_state_diff of instances a and b, 0 = the stream's own stage; between chunks) and destroyed. A shadow's sticky time-out flag is copied back
+ * in stream order and names that instance in the "in-launch hand-off of the fxcm" message. NO REPAIR: the network has consumed the columns. Coexists
+ * with _set_verify, _set_shadow, _set_shadow_repair, _set_ctx_shadow, _set_lstm_shadow, _set_journal and _set_tolerance. A handle that decodes
+ * (cmx_pipeline_late_start) drops the shadows: a decoder is not covered. _debug_fxcm_shadow_xor: the test hook cmx_fxcm_debug_state_xor on one
+ * instance, between chunks. */
+int cmx_pipeline_set_fxcm_shadow(cmx_pipeline_t*, int k);
+int cmx_pipeline_fxcm_shadow_report(cmx_pipeline_t*, uint64_t out[8]);
+int cmx_pipeline_fxcm_shadow_values(cmx_pipeline_t*, uint32_t words[3 * CMX_FXCMVOTE_COLS], uint32_t* bit, uint32_t* byte);
+int cmx_pipeline_fxcm_shadow_state_diff(cmx_pipeline_t*, int a, int b, uint64_t out[CMX_FXCM_STATE_OUT]);
+int cmx_pipeline_debug_fxcm_shadow_xor(cmx_pipeline_t*, int instance, int region, uint64_t index, uint32_t xor_mask);
 int cmx_pipeline_mixnet_mode(cmx_pipeline_t*);
 /* STREAM JOURNAL (opt-in; log2_block_bits = 0 off, the default: nothing is allocated, launched or waited for; else 6..19, 19 = the 64 KB block
  * of oracle/ref_long_trace.cpp; before the first chunk). Behind every chunk's mixing network, on the same stream, cmx_journal's kernel digests what

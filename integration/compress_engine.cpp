@@ -150,6 +150,9 @@ int main(int argc, char* argv[]) {
     // CMIX_LSTM_SHADOW=1|2: that many shadow LSTM stages vote on every chunk's distributions, bit predictions and ex; a disagreement stops the program
     const char* lsh = getenv("CMIX_LSTM_SHADOW");
     if (lsh && (lsh[0] == '1' || lsh[0] == '2') && cmx_pipeline_set_lstm_shadow(p.pipe(), lsh[0] - '0')) Predictor::Die();
+    // CMIX_FXCM_SHADOW=1|2: that many shadow fxcm stages vote on every chunk's 431 columns; a disagreement stops the program
+    const char* fsh = getenv("CMIX_FXCM_SHADOW");
+    if (fsh && (fsh[0] == '1' || fsh[0] == '2') && cmx_pipeline_set_fxcm_shadow(p.pipe(), fsh[0] - '0')) Predictor::Die();
     // CMIX_JOURNAL=path [CMIX_JOURNAL_LOG2=k, default 19 = 64 KB]: per-block digests of what the mixing network read and wrote, to `path` and `path.inputs` as the run goes
     const char* jr = getenv("CMIX_JOURNAL");
     const char* jl = getenv("CMIX_JOURNAL_LOG2");

@@ -65,6 +65,9 @@ class Predictor {
     // CMIX_LSTM_SHADOW=1|2: that many shadow LSTM stages run beside the stream's own and vote on every chunk's distributions, bit predictions and ex (a decoder is not covered)
     const char* lsh = getenv("CMIX_LSTM_SHADOW");
     if (lsh && (lsh[0] == '1' || lsh[0] == '2') && cmx_set_lstm_shadow(h_, lsh[0] - '0')) Die();
+    // CMIX_FXCM_SHADOW=1|2: that many shadow fxcm stages run beside the stream's own and vote on every chunk's 431 columns (a decoder is not covered)
+    const char* fsh = getenv("CMIX_FXCM_SHADOW");
+    if (fsh && (fsh[0] == '1' || fsh[0] == '2') && cmx_set_fxcm_shadow(h_, fsh[0] - '0')) Die();
     // CMIX_JOURNAL=path [CMIX_JOURNAL_LOG2=k, default 19 = 64 KB]: per-block digests of what the mixing network read and wrote go to `path` and `path.inputs` as the
     // run goes (-c: all 179 words per block, from the device; -d: the p and bits words, folded on this thread). CMIX_JOURNAL_CHECK=path (-d): the decode is held to a
     // compressor's journal block by block and stops at the first block whose p or bits word differs (the block size comes from that file). cmx_create reads the three
