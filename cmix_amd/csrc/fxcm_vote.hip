@@ -4,14 +4,15 @@
 // The fxcm stage (fxcm_stage.hip) writes 431 of the 2078 layer-0 columns (3..433) from 4.4 GB of tables that learn online -- one wrong word stays for
 // good -- and its roles kernel hands rows between role M's sixteen free-running wavefronts, role U and role X behind counters inside every launch.
 // Verify mode and the other votes take its columns as given. The guard here is the one the mixing network, the context stage and the LSTM have: the
-// unchanged cmx_fxcm_roles_kernel runs on two or three FxDev (cmx_fxcm_run / cmx_fxcm_run_shared) and two new kernels compare what they wrote.
+// unchanged cmx_fxcm_roles_kernel runs on two or three FxDev (cmx_fxcm_run / cmx_fxcm_run_shared) and two kernels compare what they wrote.
+// The rule, the record and the handle's plumbing: cmx_vote_core.h.
 //
 //   cmx_fxcmvote_kernel         every chunk: the 431 exported values of every bit of n = 2 or 3 instances, word for word; one wavefront per row
 //                               (a row's words are consecutive: seven coalesced 4-byte loads per lane and instance, all issued before the first
 //                               compare; no LDS). Instance 0 is read in place from the slot's layer-0 rows, whose base (layer0 + 3 + 2078 t) is only
 //                               4-byte aligned, differently from row to row: nothing wider than a 4-byte load is used.
 //   cmx_fxcmvote_fold_kernel    behind it: folds the chunk's result into a sticky record and captures the first differing bit's row
-//   cmx_fxcm_state_diff_kernel  after an event (and in tests): every word of two handles' tables in HBM
+//   cmx_state_diff_kernel       after an event (and in tests): every word of two handles' tables in HBM
 //
 // Out of scope: REPAIR (the mixing network has consumed the columns before the host sees the vote: the pipeline stops at the first event), the host
 // parser's records, the chunk's bytes and the LSTM hints (one copy of each, read by every instance: NOT covered by the vote), paq8 and PPMd, the
@@ -24,10 +25,9 @@
 #include <vector>
 
 #include "../../include/cmix_amd.h"
+#include "cmx_vote_core.h"
 #include "fxcm_rec.h"
 #include "fxcm_state.h"
-
-void cmx_set_err(const std::string& s);  // cmx_api.hip
 
 namespace {
 constexpr unsigned long long kNone = ~0ull;
@@ -36,41 +36,29 @@ constexpr int kPasses = (kCols + 63) / 64;   // 7: six full passes of the wave a
 static_assert(kCols == FX_OUTPUTS, "the vote's row is FXCM::Predict()'s 431 values of one bit");
 static_assert(CMX_FXCM_STATE_REGIONS == FX_STATE_REGIONS && CMX_FXCM_STATE_ARRAYS == FX_STATE_ARRAYS, "region and array counts of the header and of fxcm_state.h");
 
-// device block of a vote handle
-struct FxVoteDev {
-  unsigned long long rec[8];     // the sticky record (cmx_fxcmvote_report)
-  unsigned long long last[4];    // the chunk folded last (cmx_fxcmvote_last), right behind the record: one copy fetches both
-  unsigned long long key;        // this chunk: min over non-agreeing elements of (e << 2 | odd instance, 3 = no majority); ~0 = none
-  unsigned long long cnt;        // this chunk: non-agreeing elements
-  unsigned long long odd;        // this chunk: bit i = instance i was the odd one of some element, bit 3 = some element had no majority
-  unsigned long long pad;
-  uint32_t words[3 * kCols];     // capture of the first event's bit: instance i, column c at [i * 431 + c]
-  uint32_t bit, byte;            // the bit coded at that row and the byte it belongs to
-};
 struct FxVoteArgs {
   const uint32_t* rows[3];       // row t of instance i at rows[i] + t * pstride[i]
   unsigned long long pstride[3];
 };
-
-// one element of n instances: 0 agree, else 1 + (odd instance, 3 = no majority)
-template <int N>
-__device__ __forceinline__ unsigned vote_one(uint32_t a, uint32_t b, uint32_t c) {
-  if (N == 2) return a == b ? 0u : 4u;
-  if (a == b && b == c) return 0u;
-  if (b == c) return 1u;
-  if (a == c) return 2u;
-  if (a == b) return 3u;
-  return 4u;
-}
+// device block of a vote handle
+struct FxVoteDev {
+  VoteHead head;
+  uint32_t words[3 * kCols];     // capture of the first event's bit: instance i, column c at [i * 431 + c]
+  uint32_t bit, byte;            // the bit coded at that row and the byte it belongs to
+};
+struct FxRow {   // (the fold's capture; the vote kernel loads its rows itself)
+  typedef FxVoteArgs Args;
+  static constexpr int kCols = ::kCols;
+  static __device__ __forceinline__ uint32_t word(const FxVoteArgs& a, int i, unsigned long long t, unsigned c) { return a.rows[i][t * a.pstride[i] + c]; }
+};
 
 // One wavefront per row (bit), grid-stride over the rows. Every lane keeps its own minimum key, count and odd mask; one reduction and one atomic per
 // wave at the end, and only in waves that saw a difference. Registers only.
 template <int N>
-__global__ void __launch_bounds__(256) cmx_fxcmvote_kernel(FxVoteArgs a, unsigned long long nrows, FxVoteDev* d) {
+__global__ void __launch_bounds__(256) cmx_fxcmvote_kernel(FxVoteArgs a, unsigned long long nrows, VoteHead* d) {
   const unsigned lane = threadIdx.x & 63;
   const unsigned long long waves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
-  unsigned long long key = kNone, cnt = 0;
-  unsigned odd = 0;
+  VoteAcc acc;
   for (unsigned long long t = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); t < nrows; t += waves) {
     const uint32_t* r0 = a.rows[0] + t * a.pstride[0];
     const uint32_t* r1 = a.rows[1] + t * a.pstride[1];
@@ -84,71 +72,30 @@ __global__ void __launch_bounds__(256) cmx_fxcmvote_kernel(FxVoteArgs a, unsigne
     }
 #pragma unroll
     for (int p = 0; p < kPasses; ++p) {
-      const unsigned r = vote_one<N>(w0[p], w1[p], w2[p]);
-      if (r) {
-        const unsigned long long k = ((t * kCols + (lane + 64u * p)) << 2) | (r - 1);
-        key = k < key ? k : key; ++cnt; odd |= 1u << (r - 1);
-      }
+      const unsigned r = cmx_vote_one<N>(w0[p], w1[p], w2[p]);
+      if (r) acc.note(t * kCols + (lane + 64u * p), r);
     }
   }
-  if (__ballot(cnt != 0) == 0) return;   // (wave-uniform) nothing differed in this wave
-  for (int o = 32; o; o >>= 1) {
-    const unsigned long long k2 = __shfl_xor(key, o), c2 = __shfl_xor(cnt, o);
-    key = k2 < key ? k2 : key; cnt += c2; odd |= __shfl_xor(odd, o);
-  }
-  if (lane == 0) { atomicMin(&d->key, key); atomicAdd(&d->cnt, cnt); atomicOr(&d->odd, (unsigned long long)odd); }
+  acc.flush(d);
 }
 
-// one wave, behind the vote kernel on the same stream: the chunk's key and count into the sticky record; the first event's row is captured.
-// The chunk's OWN result goes into last[] exactly as cmx_vote_fold_kernel (mixnet_vote.hip) leaves it.
+// behind the vote kernel: the core's fold, and the first event's row is captured with the bit coded there and its byte
 __global__ void cmx_fxcmvote_fold_kernel(FxVoteArgs a, unsigned long long nrows, unsigned long long bit0, int n, const uint8_t* bytes, FxVoteDev* d) {
-  const unsigned long long key = d->key, cnt = d->cnt, odd = d->odd;
-  const bool first = cnt != 0 && d->rec[3] == 0;   // (read by every lane before lane 0 writes: one wave, the barrier below orders it)
-  __syncthreads();
-  const unsigned long long e = key >> 2, t = e / kCols, c = e - t * kCols;
-  if (first && t < nrows)
-    for (int i = threadIdx.x; i < n * kCols; i += blockDim.x) {
-      const int inst = i / kCols;
-      d->words[i] = a.rows[inst][t * a.pstride[inst] + (unsigned)(i - inst * kCols)];
-    }
+  const VoteEvent ev = cmx_vote_fold(&d->head, nrows, bit0, n, kCols);
+  if (!ev.capture) return;
+  cmx_vote_capture<FxRow>(a, n, ev.row, d->words);
   if (threadIdx.x == 0) {
-    d->rec[0] += 1; d->rec[1] += nrows; d->rec[2] = (unsigned long long)n;
-    if (cnt) d->rec[3] += 1;
-    if (first) {
-      d->rec[4] = bit0 + t; d->rec[5] = c; d->rec[6] = (key & 3) == 3 ? kNone : (key & 3); d->rec[7] = cnt;
-      const uint32_t by = bytes && t < nrows ? bytes[t >> 3] : 0u;
-      d->byte = by; d->bit = (by >> (7 - (unsigned)(t & 7))) & 1u;
-    }
-    d->last[0] = cnt; d->last[1] = cnt ? bit0 + t : 0; d->last[2] = cnt ? c : 0;
-    d->last[3] = !cnt ? 0 : odd == 1 ? 0 : odd == 2 ? 1 : odd == 4 ? 2 : kNone;
-    d->key = kNone; d->cnt = 0; d->odd = 0;   // the next chunk starts clean
+    const uint32_t by = bytes ? bytes[ev.row >> 3] : 0u;
+    d->byte = by; d->bit = (by >> (7 - (unsigned)(ev.row & 7))) & 1u;
   }
 }
 
-// ---- state diff: the words of two arrays; one launch per array ----
-struct FxDiffDev { unsigned long long cnt, first; };
-__global__ void __launch_bounds__(256) cmx_fxcm_state_diff_kernel(const uint32_t* x, const uint32_t* y, unsigned long long n, FxDiffDev* d) {
-  const unsigned long long nq = n / 4, items = nq + (n - 4 * nq);   // (every array is a hipMalloc of its own: 16-byte aligned)
-  unsigned long long first = kNone, cnt = 0;
-  auto word = [&](unsigned long long i) { ++cnt; first = i < first ? i : first; };
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * blockDim.x) {
-    if (i < nq) {
-      const uint4 u = reinterpret_cast<const uint4*>(x)[i], v = reinterpret_cast<const uint4*>(y)[i];
-      if (u.x != v.x) word(4 * i);
-      if (u.y != v.y) word(4 * i + 1);
-      if (u.z != v.z) word(4 * i + 2);
-      if (u.w != v.w) word(4 * i + 3);
-    } else {
-      const unsigned long long j = 4 * nq + (i - nq);
-      if (x[j] != y[j]) word(j);
-    }
-  }
-  if (__ballot(cnt != 0) == 0) return;
-  for (int o = 32; o; o >>= 1) {
-    const unsigned long long f2 = __shfl_xor(first, o), c2 = __shfl_xor(cnt, o);
-    first = f2 < first ? f2 : first; cnt += c2;
-  }
-  if ((threadIdx.x & 63) == 0) { atomicMin(&d->first, first); atomicAdd(&d->cnt, cnt); }
+// the handle's state arrays as the core's
+int fx_arrays(cmx_fxcm_t* h, std::vector<StateArray>& a, int* device, uint64_t* bytes_done) {
+  std::vector<FxRegion> rg(FX_STATE_ARRAYS); int n = 0;
+  if (cmx_fxcm_state_view(h, rg.data(), &n, device, bytes_done)) return 1;
+  a = state_arrays(rg.data(), n);
+  return 0;
 }
 
 // cmx_fxcm_debug_state_xor, region by region: may a word with ANY value be handed to the unchanged kernels? Decided by reading every use of the
@@ -179,39 +126,12 @@ const char* const kRegionName[FX_STATE_REGIONS] = {"constant tables", "map bucke
                                                    "APM tables", "FxDev scalars"};
 }  // namespace
 
-struct cmx_fxcmvote {
-  int device = 0, n = 0;
-  FxVoteDev* d = nullptr;
-};
+struct cmx_fxcmvote : VoteHandle {};
 
 extern "C" {
 
-cmx_fxcmvote_t* cmx_fxcmvote_create(int device, int n) {
-  if (n != 2 && n != 3) { cmx_set_err("cmx_fxcmvote_create: n must be 2 or 3 instances"); return nullptr; }
-  if (cmx_device_count() <= 0) { cmx_set_err("cmx_fxcmvote_create: no HIP device visible (a gfx950 GPU is required)"); return nullptr; }
-  if (device < 0 || device >= cmx_device_count() || hipSetDevice(device) != hipSuccess) { cmx_set_err("cmx_fxcmvote_create: bad device index"); return nullptr; }
-  cmx_fxcmvote_t* v = new cmx_fxcmvote();
-  v->device = device; v->n = n;
-  FxVoteDev init;
-  memset(&init, 0, sizeof init);
-  init.key = kNone;
-  if (hipMalloc((void**)&v->d, sizeof(FxVoteDev)) != hipSuccess || hipMemcpy(v->d, &init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError();
-    if (v->d) (void)hipFree(v->d);
-    delete v;
-    cmx_set_err("cmx_fxcmvote_create: hipMalloc failed");
-    return nullptr;
-  }
-  return v;
-}
-
-void cmx_fxcmvote_destroy(cmx_fxcmvote_t* v) {
-  if (!v) return;
-  (void)hipSetDevice(v->device);
-  (void)hipDeviceSynchronize();
-  if (v->d) (void)hipFree(v->d);
-  delete v;
-}
+cmx_fxcmvote_t* cmx_fxcmvote_create(int device, int n) { return vote_create<cmx_fxcmvote>("cmx_fxcmvote_create", device, n, sizeof(FxVoteDev)); }
+void cmx_fxcmvote_destroy(cmx_fxcmvote_t* v) { vote_destroy(v); }
 
 int cmx_fxcmvote_run(cmx_fxcmvote_t* v, const float* const* d_rows, const size_t* pstride, size_t nbits, uint64_t stream_bit0, const uint8_t* d_bytes, void* stream) {
   if (!v || !d_rows || !pstride) { cmx_set_err("cmx_fxcmvote_run: bad argument"); return 1; }
@@ -228,85 +148,50 @@ int cmx_fxcmvote_run(cmx_fxcmvote_t* v, const float* const* d_rows, const size_t
   if (hipSetDevice(v->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   hipStream_t st = (hipStream_t)stream;
   const unsigned long long nrows = nbits;
-  const unsigned grid = (unsigned)((nrows + 3) / 4 < 512 ? (nrows + 3) / 4 : 512);   // four rows (waves) per workgroup; 2048 waves stride over the rest
-  if (v->n == 3) hipLaunchKernelGGL(cmx_fxcmvote_kernel<3>, dim3(grid), dim3(256), 0, st, a, nrows, v->d);
-  else hipLaunchKernelGGL(cmx_fxcmvote_kernel<2>, dim3(grid), dim3(256), 0, st, a, nrows, v->d);
-  hipLaunchKernelGGL(cmx_fxcmvote_fold_kernel, dim3(1), dim3(64), 0, st, a, nrows, (unsigned long long)stream_bit0, v->n, d_bytes, v->d);
+  if (v->n == 3) hipLaunchKernelGGL(cmx_fxcmvote_kernel<3>, dim3(vote_row_grid(nrows)), dim3(256), 0, st, a, nrows, v->d);
+  else hipLaunchKernelGGL(cmx_fxcmvote_kernel<2>, dim3(vote_row_grid(nrows)), dim3(256), 0, st, a, nrows, v->d);
+  hipLaunchKernelGGL(cmx_fxcmvote_fold_kernel, dim3(1), dim3(64), 0, st, a, nrows, (unsigned long long)stream_bit0, v->n, d_bytes, (FxVoteDev*)v->d);
   if (hipGetLastError() != hipSuccess) { cmx_set_err("cmx_fxcmvote_run: kernel launch failed"); return 1; }
   return 0;
 }
 
 const unsigned long long* cmx_fxcmvote_record(cmx_fxcmvote_t* v) { return v && v->d ? v->d->rec : nullptr; }
 
-int cmx_fxcmvote_report(cmx_fxcmvote_t* v, uint64_t out[8]) {
-  if (!v || !out) { cmx_set_err("cmx_fxcmvote_report: bad argument"); return 1; }
-  unsigned long long r[8];
-  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(r, v->d->rec, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) {
-    cmx_set_err("cmx_fxcmvote_report: device error"); return 1;
-  }
-  for (int i = 0; i < 8; ++i) out[i] = r[i];
-  return 0;
-}
-
-int cmx_fxcmvote_last(cmx_fxcmvote_t* v, uint64_t out[4]) {
-  if (!v || !out) { cmx_set_err("cmx_fxcmvote_last: bad argument"); return 1; }
-  unsigned long long r[4];
-  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(r, v->d->last, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) {
-    cmx_set_err("cmx_fxcmvote_last: device error"); return 1;
-  }
-  for (int i = 0; i < 4; ++i) out[i] = r[i];
-  return 0;
-}
+int cmx_fxcmvote_report(cmx_fxcmvote_t* v, uint64_t out[8]) { return vote_report("cmx_fxcmvote_report", v, out); }
+int cmx_fxcmvote_last(cmx_fxcmvote_t* v, uint64_t out[4]) { return vote_last("cmx_fxcmvote_last", v, out); }
 
 int cmx_fxcmvote_values(cmx_fxcmvote_t* v, uint32_t words[3 * CMX_FXCMVOTE_COLS], uint32_t* bit, uint32_t* byte) {
-  if (!v || !words) { cmx_set_err("cmx_fxcmvote_values: bad argument"); return 1; }
-  std::vector<FxVoteDev> h(1);
-  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(h.data(), v->d, sizeof(FxVoteDev), hipMemcpyDeviceToHost) != hipSuccess) {
-    cmx_set_err("cmx_fxcmvote_values: device error"); return 1;
-  }
-  memcpy(words, h[0].words, sizeof h[0].words);
-  if (bit) *bit = h[0].bit;
-  if (byte) *byte = h[0].byte;
+  FxVoteDev h;
+  if (vote_values("cmx_fxcmvote_values", v, words, &h)) return 1;
+  memcpy(words, h.words, sizeof h.words);
+  if (bit) *bit = h.bit;
+  if (byte) *byte = h.byte;
   return 0;
 }
 
 int cmx_fxcm_state_diff(cmx_fxcm_t* a, cmx_fxcm_t* b, uint64_t out[CMX_FXCM_STATE_OUT]) {
   if (!a || !b || !out) { cmx_set_err("cmx_fxcm_state_diff: bad argument"); return 1; }
   if (a == b) { cmx_set_err("cmx_fxcm_state_diff: a and b are the same handle"); return 1; }
-  std::vector<FxRegion> ra(FX_STATE_ARRAYS), rb(FX_STATE_ARRAYS);
-  int na = 0, nb = 0, deva = 0, devb = 0;
+  std::vector<StateArray> ra, rb; int deva = 0, devb = 0;
   uint64_t ca = 0, cb = 0;
-  if (cmx_fxcm_state_view(a, ra.data(), &na, &deva, &ca) || cmx_fxcm_state_view(b, rb.data(), &nb, &devb, &cb)) return 1;
+  if (fx_arrays(a, ra, &deva, &ca) || fx_arrays(b, rb, &devb, &cb)) return 1;
+  const int na = (int)ra.size();
   if (deva != devb) { cmx_set_err("cmx_fxcm_state_diff: the two handles live on different devices"); return 1; }
   if (ca != cb) { cmx_set_err("cmx_fxcm_state_diff: the host-side counter bytes_done differs: " + std::to_string(ca) + " and " + std::to_string(cb)); return 1; }
   if (hipSetDevice(deva) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_fxcm_state_diff: device error"); return 1; }
-  std::vector<FxDiffDev> h((size_t)na, FxDiffDev{0, kNone});
-  FxDiffDev* d = nullptr;
-  bool ok = na == nb && hipMalloc((void**)&d, h.size() * sizeof(FxDiffDev)) == hipSuccess && hipMemcpy(d, h.data(), h.size() * sizeof(FxDiffDev), hipMemcpyHostToDevice) == hipSuccess;
-  for (int r = 0; ok && r < na; ++r) {
-    if (ra[r].region != rb[r].region || ra[r].words != rb[r].words) { ok = false; break; }
-    const unsigned long long items = ra[r].words / 4 + 4;
-    const unsigned grid = (unsigned)(items / 256 + 1 < 2048 ? items / 256 + 1 : 2048);
-    hipLaunchKernelGGL(cmx_fxcm_state_diff_kernel, dim3(grid), dim3(256), 0, 0, ra[r].p, rb[r].p, ra[r].words, d + r);
-    ok = hipGetLastError() == hipSuccess;
-  }
-  ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(h.data(), d, h.size() * sizeof(FxDiffDev), hipMemcpyDeviceToHost) == hipSuccess;
+  std::vector<DiffDev> h(ra.size());
+  bool ok = ra.size() == rb.size() && state_diff_arrays(ra.data(), rb.data(), na, 2048, h.data());
   for (int i = 0; i < CMX_FXCM_STATE_OUT; ++i) out[i] = 0;
   for (int i = 1; i <= 4; ++i) out[i] = kNone;
-  unsigned long long off = 0;   // of array r inside its region
   for (int r = 0; ok && r < na; ++r) {   // (region-then-array order)
-    if (r && ra[r].region != ra[r - 1].region) off = 0;
-    if (h[r].cnt) {
-      out[0] += h[r].cnt; out[5 + ra[r].region] += h[r].cnt;
-      if (out[1] == kNone) {
-        uint32_t x = 0, y = 0;
-        ok = hipMemcpy(&x, ra[r].p + h[r].first, 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(&y, rb[r].p + h[r].first, 4, hipMemcpyDeviceToHost) == hipSuccess;
-        out[1] = (uint64_t)ra[r].region; out[2] = off + h[r].first; out[3] = x; out[4] = y;
-      }
+    if (!h[r].cnt) continue;
+    out[0] += h[r].cnt; out[5 + ra[r].region] += h[r].cnt;
+    if (out[1] == kNone) {
+      uint32_t x = 0, y = 0;
+      ok = state_fetch_pair(ra[r], rb[r], h[r].first, &x, &y);
+      out[1] = (uint64_t)ra[r].region; out[2] = state_offset(ra.data(), r) + h[r].first; out[3] = x; out[4] = y;
     }
-    off += ra[r].words;
   }
-  if (d) (void)hipFree(d);
   if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_fxcm_state_diff: device error"); return 1; }
   // region 11: FxDev itself, device pointers zeroed (they differ between two handles by construction)
   std::vector<uint32_t> wa, wb;
@@ -328,24 +213,12 @@ int cmx_fxcm_debug_state_xor(cmx_fxcm_t* h, int region, uint64_t index, uint32_t
                 ") holds words the kernels address memory or bound loops with: refused (the hook changes values only)");
     return 1;
   }
-  std::vector<FxRegion> rg(FX_STATE_ARRAYS);
-  int n = 0, dev = 0;
-  if (cmx_fxcm_state_view(h, rg.data(), &n, &dev, nullptr)) return 1;
-  uint32_t* p = nullptr;
-  unsigned long long off = 0;
-  for (int r = 0; r < n && !p; ++r) {
-    if (r && rg[r].region != rg[r - 1].region) off = 0;
-    if (rg[r].region == region && index >= off && index - off < rg[r].words) p = rg[r].p + (index - off);
-    off += rg[r].words;
-  }
+  std::vector<StateArray> rg; int dev = 0;
+  if (fx_arrays(h, rg, &dev, nullptr)) return 1;
+  const int n = (int)rg.size();
+  uint32_t* p = state_word(rg.data(), n, region, index);
   if (!p) { cmx_set_err("cmx_fxcm_debug_state_xor: no such word (region, index out of range)"); return 1; }
-  uint32_t x = 0;
-  if (hipSetDevice(dev) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&x, p, 4, hipMemcpyDeviceToHost) != hipSuccess) {
-    cmx_set_err("cmx_fxcm_debug_state_xor: device error"); return 1;
-  }
-  x ^= xor_mask;
-  if (hipMemcpy(p, &x, 4, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_fxcm_debug_state_xor: device error"); return 1; }
-  return 0;
+  return state_xor("cmx_fxcm_debug_state_xor", dev, p, xor_mask);
 }
 
 int cmx_fxcm_debug_state_read(cmx_fxcm_t* h, int region, uint64_t index, uint64_t count, uint32_t* out) {
@@ -358,19 +231,18 @@ int cmx_fxcm_debug_state_read(cmx_fxcm_t* h, int region, uint64_t index, uint64_
     memcpy(out, w.data() + index, count * 4);
     return 0;
   }
-  std::vector<FxRegion> rg(FX_STATE_ARRAYS);
-  int n = 0, dev = 0;
-  if (cmx_fxcm_state_view(h, rg.data(), &n, &dev, nullptr)) return 1;
+  std::vector<StateArray> rg; int dev = 0;
+  if (fx_arrays(h, rg, &dev, nullptr)) return 1;
+  const int n = (int)rg.size();
   if (hipSetDevice(dev) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_fxcm_debug_state_read: device error"); return 1; }
-  unsigned long long off = 0, done = 0;
+  unsigned long long done = 0;
   for (int r = 0; r < n && done < count; ++r) {   // (the words may run from one array of the region into the next)
-    if (r && rg[r].region != rg[r - 1].region) off = 0;
+    const unsigned long long off = state_offset(rg.data(), r);
     if (rg[r].region == region && index + done >= off && index + done - off < rg[r].words) {
       const unsigned long long at = index + done - off, m = count - done < rg[r].words - at ? count - done : rg[r].words - at;
       if (hipMemcpy(out + done, rg[r].p + at, m * 4, hipMemcpyDeviceToHost) != hipSuccess) { cmx_set_err("cmx_fxcm_debug_state_read: device error"); return 1; }
       done += m;
     }
-    off += rg[r].words;
   }
   if (done != count) { cmx_set_err("cmx_fxcm_debug_state_read: no such words (region, index out of range)"); return 1; }
   return 0;
@@ -378,15 +250,10 @@ int cmx_fxcm_debug_state_read(cmx_fxcm_t* h, int region, uint64_t index, uint64_
 
 int cmx_fxcm_debug_layout(cmx_fxcm_t* h, uint64_t out[3 * CMX_FXCM_STATE_ARRAYS]) {
   if (!h || !out) { cmx_set_err("cmx_fxcm_debug_layout: bad argument"); return -1; }
-  std::vector<FxRegion> rg(FX_STATE_ARRAYS);
-  int n = 0, dev = 0;
-  if (cmx_fxcm_state_view(h, rg.data(), &n, &dev, nullptr)) return -1;
-  unsigned long long off = 0;
-  for (int r = 0; r < n; ++r) {
-    if (r && rg[r].region != rg[r - 1].region) off = 0;
-    out[3 * r] = (uint64_t)rg[r].region; out[3 * r + 1] = off; out[3 * r + 2] = rg[r].words;
-    off += rg[r].words;
-  }
+  std::vector<StateArray> rg; int dev = 0;
+  if (fx_arrays(h, rg, &dev, nullptr)) return -1;
+  const int n = (int)rg.size();
+  state_layout(rg.data(), n, out);
   std::vector<uint32_t> w;
   if (cmx_fxcm_dev_words(h, w)) return -1;
   out[3 * n] = FX_REGION_DEV; out[3 * n + 1] = 0; out[3 * n + 2] = w.size();

@@ -22,10 +22,10 @@
 #include <string>
 
 #include "../../include/cmix_amd.h"
+#include "cmx_vote_core.h"
 #include "mixnet_state.h"
 #include "cmx_verify.h"
 
-void cmx_set_err(const std::string& s);  // cmx_api.hip
 extern "C" int cmx_mixnet_state_view(cmx_mixnet_t* h, const MixState** host, MixState** dev, int* device);   // cmx_api.hip
 extern "C" unsigned long long* cmx_mixnet_verify_segments(cmx_mixnet_t* h);   // cmx_api.hip: a verifying handle's stored row-segment digests, else NULL
 extern "C" int cmx_mixnet_state_refresh(cmx_mixnet_t* h);                     // cmx_api.hip: the host copy of the block's scalars, from the device
@@ -34,58 +34,44 @@ namespace {
 constexpr unsigned long long kNone = ~0ull;
 constexpr int kCols = CMX_MIXERS + 1;   // 47 mixer outputs, then the final p: the causal order within a bit
 
-// device block of a vote handle
-struct VoteDev {
-  unsigned long long rec[8];     // the sticky record (cmx_vote_report)
-  unsigned long long last[4];    // the chunk folded last (cmx_vote_last), right behind the record: one copy fetches both
-  unsigned long long key;        // this chunk: min over non-agreeing elements of (e << 2 | odd instance, 3 = no majority); ~0 = none
-  unsigned long long cnt;        // this chunk: non-agreeing elements
-  unsigned long long odd;        // this chunk: bit i = instance i was the odd one of some element, bit 3 = some element had no majority
-  unsigned long long pad;
-  uint32_t words[3 * kCols];     // capture of the first event's bit: instance i, column c at [i * 48 + c]
-  uint32_t sel[CMX_MIXERS];
-  uint32_t bit;
-};
 struct VoteArgs {
   const uint32_t* p[3];
   const uint32_t* mix[3];
 };
-
-// one element of n instances: 0 agree, else 1 + (odd instance, 3 = no majority)
-template <int N>
-__device__ __forceinline__ unsigned vote_one(uint32_t a, uint32_t b, uint32_t c) {
-  if (N == 2) return a == b ? 0u : 4u;
-  if (a == b && b == c) return 0u;
-  if (b == c) return 1u;
-  if (a == c) return 2u;
-  if (a == b) return 3u;
-  return 4u;
-}
+// device block of a vote handle
+struct VoteDev {
+  VoteHead head;
+  uint32_t words[3 * kCols];     // capture of the first event's bit: instance i, column c at [i * 48 + c]
+  uint32_t sel[CMX_MIXERS];
+  uint32_t bit;
+};
+struct MixRow {   // (the fold's capture; the vote kernel walks the flat arrays itself)
+  typedef VoteArgs Args;
+  static constexpr int kCols = ::kCols;
+  static __device__ __forceinline__ uint32_t word(const VoteArgs& a, int i, unsigned long long t, unsigned c) {
+    return c < CMX_MIXERS ? a.mix[i][t * CMX_MIXERS + c] : a.p[i][t];
+  }
+};
 
 // Items: [0, nq) quads of the flat mix arrays, [nq, nq + pq) quads of p, then the single words either array has left over (all of them when an
 // array is not 16-byte aligned: vec == 0). Every lane keeps its own minimum key and count; one reduction per wave at the end.
 template <int N>
-__global__ void __launch_bounds__(256) cmx_vote_kernel(VoteArgs a, unsigned long long nbits, int vec, VoteDev* d) {
+__global__ void __launch_bounds__(256) cmx_vote_kernel(VoteArgs a, unsigned long long nbits, int vec, VoteHead* d) {
   const unsigned long long nmix = nbits * CMX_MIXERS;
   const unsigned long long nq = vec ? nmix / 4 : 0, pq = vec ? nbits / 4 : 0;
   const unsigned long long mt = nmix - 4 * nq, pt = nbits - 4 * pq;
   const unsigned long long items = nq + pq + mt + pt;
-  unsigned long long key = kNone, cnt = 0;
-  unsigned odd = 0;
+  VoteAcc acc;
   auto mixword = [&](unsigned long long f, uint32_t w0, uint32_t w1, uint32_t w2) {
-    const unsigned r = vote_one<N>(w0, w1, w2);
+    const unsigned r = cmx_vote_one<N>(w0, w1, w2);
     if (r) {
       const unsigned long long t = f / CMX_MIXERS, c = f - t * CMX_MIXERS;
-      const unsigned long long k = ((t * kCols + c) << 2) | (r - 1);
-      key = k < key ? k : key; ++cnt; odd |= 1u << (r - 1);
+      acc.note(t * kCols + c, r);
     }
   };
   auto pword = [&](unsigned long long t, uint32_t w0, uint32_t w1, uint32_t w2) {
-    const unsigned r = vote_one<N>(w0, w1, w2);
-    if (r) {
-      const unsigned long long k = ((t * kCols + CMX_MIXERS) << 2) | (r - 1);
-      key = k < key ? k : key; ++cnt; odd |= 1u << (r - 1);
-    }
+    const unsigned r = cmx_vote_one<N>(w0, w1, w2);
+    if (r) acc.note(t * kCols + CMX_MIXERS, r);
   };
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * blockDim.x) {
     if (i < nq + pq) {
@@ -106,114 +92,36 @@ __global__ void __launch_bounds__(256) cmx_vote_kernel(VoteArgs a, unsigned long
       pword(t, a.p[0][t], a.p[1][t], N == 3 ? a.p[2][t] : a.p[1][t]);
     }
   }
-  if (__ballot(cnt != 0) == 0) return;   // (wave-uniform) nothing differed in this wave
-  for (int o = 32; o; o >>= 1) {
-    const unsigned long long k2 = __shfl_xor(key, o), c2 = __shfl_xor(cnt, o);
-    key = k2 < key ? k2 : key; cnt += c2; odd |= __shfl_xor(odd, o);
-  }
-  if ((threadIdx.x & 63) == 0) { atomicMin(&d->key, key); atomicAdd(&d->cnt, cnt); atomicOr(&d->odd, (unsigned long long)odd); }
+  acc.flush(d);
 }
 
-// one wave, behind the vote kernel on the same stream: the chunk's key and count into the sticky record; the first event's bit is captured.
-// The chunk's OWN result goes into last[]: [0] its non-agreeing elements (0: the instances agree, the rest is 0), [1] the stream bit and [2] the
-// column of the first of them, [3] the odd instance -- the one instance that was odd wherever the chunk's elements did not agree -- or ~0 for no
-// majority: an element at which all differ (or n = 2), or two elements with different odd instances.
+// behind the vote kernel: the core's fold, and the first event's bit is captured with its selectors
 __global__ void cmx_vote_fold_kernel(VoteArgs a, unsigned long long nbits, unsigned long long bit0, int n, const uint32_t* sel, const uint8_t* bits, VoteDev* d) {
-  const unsigned long long key = d->key, cnt = d->cnt, odd = d->odd;
-  const bool first = cnt != 0 && d->rec[3] == 0;   // (read by every lane before lane 0 writes: one wave, the barrier below orders it)
-  __syncthreads();
-  const unsigned long long e = key >> 2, t = e / kCols, c = e - t * kCols;
-  if (first && t < nbits) {
-    for (int i = threadIdx.x; i < n * kCols; i += blockDim.x) {
-      const int inst = i / kCols, col = i - inst * kCols;
-      d->words[i] = col < CMX_MIXERS ? a.mix[inst][t * CMX_MIXERS + col] : a.p[inst][t];
-    }
-    for (int i = threadIdx.x; i < CMX_MIXERS; i += blockDim.x) d->sel[i] = sel ? sel[t * CMX_MIXERS + i] : 0u;
-  }
-  if (threadIdx.x == 0) {
-    d->rec[0] += 1; d->rec[1] += nbits; d->rec[2] = (unsigned long long)n;
-    if (cnt) d->rec[3] += 1;
-    if (first) {
-      d->rec[4] = bit0 + t; d->rec[5] = c; d->rec[6] = (key & 3) == 3 ? kNone : (key & 3); d->rec[7] = cnt;
-      d->bit = bits && t < nbits ? bits[t] : 0u;
-    }
-    d->last[0] = cnt; d->last[1] = cnt ? bit0 + t : 0; d->last[2] = cnt ? c : 0;
-    d->last[3] = !cnt ? 0 : odd == 1 ? 0 : odd == 2 ? 1 : odd == 4 ? 2 : kNone;
-    d->key = kNone; d->cnt = 0; d->odd = 0;   // the next chunk starts clean
-  }
+  const VoteEvent ev = cmx_vote_fold(&d->head, nbits, bit0, n, kCols);
+  if (!ev.capture) return;
+  cmx_vote_capture<MixRow>(a, n, ev.row, d->words);
+  for (int i = threadIdx.x; i < CMX_MIXERS; i += blockDim.x) d->sel[i] = sel ? sel[ev.row * CMX_MIXERS + i] : 0u;
+  if (threadIdx.x == 0) d->bit = bits ? bits[ev.row] : 0u;
 }
 
-// ---- state diff: words of two arrays; per call one region ----
-struct DiffDev {
-  unsigned long long cnt, first, mask;
-  unsigned long long was;   // repair only: min over the repaired words of (word number << 32 | the word dst held), so the first one's old value survives
-};
-// per_mixer: words per mixer of the region (0: the region has no mixer mask)
-__global__ void __launch_bounds__(256) cmx_state_diff_kernel(const uint32_t* x, const uint32_t* y, unsigned long long n, unsigned long long per_mixer, DiffDev* d) {
-  const unsigned long long nq = n / 4, items = nq + (n - 4 * nq);
-  unsigned long long first = kNone, cnt = 0, mask = 0;
-  auto word = [&](unsigned long long i) {
-    ++cnt; first = i < first ? i : first;
-    if (per_mixer) mask |= 1ull << (i / per_mixer);
-  };
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * blockDim.x) {
-    if (i < nq) {
-      const uint4 u = reinterpret_cast<const uint4*>(x)[i], v = reinterpret_cast<const uint4*>(y)[i];
-      if (u.x != v.x) word(4 * i);
-      if (u.y != v.y) word(4 * i + 1);
-      if (u.z != v.z) word(4 * i + 2);
-      if (u.w != v.w) word(4 * i + 3);
-    } else {
-      const unsigned long long j = 4 * nq + (i - nq);
-      if (x[j] != y[j]) word(j);
-    }
-  }
-  if (__ballot(cnt != 0) == 0) return;
-  for (int o = 32; o; o >>= 1) {
-    const unsigned long long f2 = __shfl_xor(first, o), c2 = __shfl_xor(cnt, o), m2 = __shfl_xor(mask, o);
-    first = f2 < first ? f2 : first; cnt += c2; mask |= m2;
-  }
-  if ((threadIdx.x & 63) == 0) { atomicMin(&d->first, first); atomicAdd(&d->cnt, cnt); if (mask) atomicOr(&d->mask, mask); }
-}
-
-// ---- state repair: the diff's walk, storing y's word over every differing word of x (y is only read) ----
+// ---- state repair: the diff's walk (cmx_vote_core.h), storing y's word over every differing word of x (y is only read) ----
 // touched (region 0 of a verifying handle, else NULL): one flag per stored row segment of cmx_verify.h, [row number][CMX_VERIFY_SEGS], set where a word
 // the segment's digest covers was repaired. Only differing words are stored, with ordinary 4-byte vector stores: a clean pass writes nothing.
 __global__ void __launch_bounds__(256) cmx_state_repair_kernel(uint32_t* x, const uint32_t* y, unsigned long long n, unsigned long long per_mixer, DiffDev* d,
                                                                unsigned* touched) {
-  const unsigned long long nq = n / 4, items = nq + (n - 4 * nq);
-  unsigned long long first = kNone, cnt = 0, mask = 0, was = kNone;
-  auto word = [&](unsigned long long i, uint32_t old, uint32_t w) {
+  DiffAcc acc;
+  cmx_state_walk(x, y, n, [&](unsigned long long i, uint32_t old, uint32_t w) {
     x[i] = w;
-    ++cnt; first = i < first ? i : first;
+    acc.note(i, per_mixer);
     const unsigned long long k = (i << 32) | old;   // (every region has fewer than 2^32 words)
-    was = k < was ? k : was;
-    if (per_mixer) mask |= 1ull << (i / per_mixer);
+    acc.was = k < acc.was ? k : acc.was;
     if (touched) {
       const unsigned long long row = i / CMX_ROW0_STRIDE;
       const unsigned idx = (unsigned)(i - row * CMX_ROW0_STRIDE);
       if (idx < CMX_IN0) touched[row * CMX_VERIFY_SEGS + (idx < 2048 ? idx >> 9 : CMX_VERIFY_SEGS - 1)] = 1u;   // (the same value from every writer)
     }
-  };
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * blockDim.x) {
-    if (i < nq) {
-      const uint4 u = reinterpret_cast<const uint4*>(x)[i], v = reinterpret_cast<const uint4*>(y)[i];
-      if (u.x != v.x) word(4 * i, u.x, v.x);
-      if (u.y != v.y) word(4 * i + 1, u.y, v.y);
-      if (u.z != v.z) word(4 * i + 2, u.z, v.z);
-      if (u.w != v.w) word(4 * i + 3, u.w, v.w);
-    } else {
-      const unsigned long long j = 4 * nq + (i - nq);
-      const uint32_t u = x[j], v = y[j];
-      if (u != v) word(j, u, v);
-    }
-  }
-  if (__ballot(cnt != 0) == 0) return;
-  for (int o = 32; o; o >>= 1) {
-    const unsigned long long f2 = __shfl_xor(first, o), c2 = __shfl_xor(cnt, o), m2 = __shfl_xor(mask, o), w2 = __shfl_xor(was, o);
-    first = f2 < first ? f2 : first; cnt += c2; mask |= m2; was = w2 < was ? w2 : was;
-  }
-  if ((threadIdx.x & 63) == 0) { atomicMin(&d->first, first); atomicAdd(&d->cnt, cnt); if (mask) atomicOr(&d->mask, mask); atomicMin(&d->was, was); }
+  });
+  acc.flush<true>(d);
 }
 
 // Verify mode's stored digests of the touched layer-0 row segments, recomputed from the repaired rows: one wave per segment, the words and the sum of
@@ -295,39 +203,12 @@ unsigned long long word_of(int region, unsigned long long mixer, unsigned long l
 }
 }  // namespace
 
-struct cmx_vote {
-  int device = 0, n = 0;
-  VoteDev* d = nullptr;
-};
+struct cmx_vote : VoteHandle {};
 
 extern "C" {
 
-cmx_vote_t* cmx_vote_create(int device, int n) {
-  if (n != 2 && n != 3) { cmx_set_err("cmx_vote_create: n must be 2 or 3 instances"); return nullptr; }
-  if (cmx_device_count() <= 0) { cmx_set_err("cmx_vote_create: no HIP device visible (a gfx950 GPU is required)"); return nullptr; }
-  if (device < 0 || device >= cmx_device_count() || hipSetDevice(device) != hipSuccess) { cmx_set_err("cmx_vote_create: bad device index"); return nullptr; }
-  cmx_vote_t* v = new cmx_vote();
-  v->device = device; v->n = n;
-  VoteDev init;
-  memset(&init, 0, sizeof init);
-  init.key = kNone;
-  if (hipMalloc((void**)&v->d, sizeof(VoteDev)) != hipSuccess || hipMemcpy(v->d, &init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError();
-    if (v->d) (void)hipFree(v->d);
-    delete v;
-    cmx_set_err("cmx_vote_create: hipMalloc failed");
-    return nullptr;
-  }
-  return v;
-}
-
-void cmx_vote_destroy(cmx_vote_t* v) {
-  if (!v) return;
-  (void)hipSetDevice(v->device);
-  (void)hipDeviceSynchronize();
-  if (v->d) (void)hipFree(v->d);
-  delete v;
-}
+cmx_vote_t* cmx_vote_create(int device, int n) { return vote_create<cmx_vote>("cmx_vote_create", device, n, sizeof(VoteDev)); }
+void cmx_vote_destroy(cmx_vote_t* v) { vote_destroy(v); }
 
 int cmx_vote_run(cmx_vote_t* v, const float* const* d_p, const float* const* d_mix, size_t nbits, uint64_t stream_bit0, const uint32_t* d_sel, const uint8_t* d_bits,
                  void* stream) {
@@ -349,39 +230,19 @@ int cmx_vote_run(cmx_vote_t* v, const float* const* d_p, const float* const* d_m
   const unsigned grid = (unsigned)(items / 256 + 1 < 1024 ? items / 256 + 1 : 1024);
   if (v->n == 3) hipLaunchKernelGGL(cmx_vote_kernel<3>, dim3(grid), dim3(256), 0, st, a, (unsigned long long)nbits, vec, v->d);
   else hipLaunchKernelGGL(cmx_vote_kernel<2>, dim3(grid), dim3(256), 0, st, a, (unsigned long long)nbits, vec, v->d);
-  hipLaunchKernelGGL(cmx_vote_fold_kernel, dim3(1), dim3(64), 0, st, a, (unsigned long long)nbits, (unsigned long long)stream_bit0, v->n, d_sel, d_bits, v->d);
+  hipLaunchKernelGGL(cmx_vote_fold_kernel, dim3(1), dim3(64), 0, st, a, (unsigned long long)nbits, (unsigned long long)stream_bit0, v->n, d_sel, d_bits, (VoteDev*)v->d);
   if (hipGetLastError() != hipSuccess) { cmx_set_err("cmx_vote_run: kernel launch failed"); return 1; }
   return 0;
 }
 
 const unsigned long long* cmx_vote_record(cmx_vote_t* v) { return v && v->d ? v->d->rec : nullptr; }
 
-int cmx_vote_report(cmx_vote_t* v, uint64_t out[8]) {
-  if (!v || !out) { cmx_set_err("cmx_vote_report: bad argument"); return 1; }
-  unsigned long long r[8];
-  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(r, v->d->rec, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) {
-    cmx_set_err("cmx_vote_report: device error"); return 1;
-  }
-  for (int i = 0; i < 8; ++i) out[i] = r[i];
-  return 0;
-}
-
-int cmx_vote_last(cmx_vote_t* v, uint64_t out[4]) {
-  if (!v || !out) { cmx_set_err("cmx_vote_last: bad argument"); return 1; }
-  unsigned long long r[4];
-  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(r, v->d->last, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) {
-    cmx_set_err("cmx_vote_last: device error"); return 1;
-  }
-  for (int i = 0; i < 4; ++i) out[i] = r[i];
-  return 0;
-}
+int cmx_vote_report(cmx_vote_t* v, uint64_t out[8]) { return vote_report("cmx_vote_report", v, out); }
+int cmx_vote_last(cmx_vote_t* v, uint64_t out[4]) { return vote_last("cmx_vote_last", v, out); }
 
 int cmx_vote_values(cmx_vote_t* v, uint32_t words[144], uint32_t sel[47], uint32_t* bit) {
-  if (!v || !words) { cmx_set_err("cmx_vote_values: bad argument"); return 1; }
   VoteDev h;
-  if (hipSetDevice(v->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&h, v->d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) {
-    cmx_set_err("cmx_vote_values: device error"); return 1;
-  }
+  if (vote_values("cmx_vote_values", v, words, &h)) return 1;
   memcpy(words, h.words, sizeof h.words);
   if (sel) memcpy(sel, h.sel, sizeof h.sel);
   if (bit) *bit = h.bit;
@@ -399,25 +260,19 @@ static int state_walk(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20], bool r
   if (hipSetDevice(deva) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err(who + ": device error"); return 1; }
   Region ra[10], rb[10];
   regions_of(*ha, ra); regions_of(*hb, rb);
-  DiffDev* d = nullptr;
-  DiffDev h[kRegions];
-  memset(h, 0, sizeof h);
-  for (DiffDev& x : h) x.first = x.was = kNone;
-  bool ok = hipMalloc((void**)&d, sizeof h) == hipSuccess && hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice) == hipSuccess;
   // a verifying dst: its stored row-segment digests must follow the repaired layer-0 rows (the next reload would raise a false alarm otherwise)
   unsigned long long* vseg = repair ? cmx_mixnet_verify_segments(a) : nullptr;
   unsigned* touched = nullptr;
   const unsigned nseg = CMX_MIX0 * CMX_ROWS_PER_MIXER * CMX_VERIFY_SEGS;
-  if (ok && vseg) ok = hipMalloc((void**)&touched, (size_t)nseg * 4) == hipSuccess && hipMemset(touched, 0, (size_t)nseg * 4) == hipSuccess;
-  for (int r = 0; ok && r < 10; ++r) {
-    const unsigned long long items = ra[r].words / 4 + 4;
-    const unsigned grid = (unsigned)(items / 256 + 1 < 4096 ? items / 256 + 1 : 4096);
-    if (repair) hipLaunchKernelGGL(cmx_state_repair_kernel, dim3(grid), dim3(256), 0, 0, (uint32_t*)ra[r].p, rb[r].p, ra[r].words, ra[r].per_mixer, d + r, r == 0 ? touched : nullptr);
-    else hipLaunchKernelGGL(cmx_state_diff_kernel, dim3(grid), dim3(256), 0, 0, ra[r].p, rb[r].p, ra[r].words, ra[r].per_mixer, d + r);
-    ok = hipGetLastError() == hipSuccess;
-  }
+  bool ok = !vseg || (hipMalloc((void**)&touched, (size_t)nseg * 4) == hipSuccess && hipMemset(touched, 0, (size_t)nseg * 4) == hipSuccess);
+  DiffDev h[kRegions];
+  for (DiffDev& x : h) x = {0, kNone, 0, kNone};   // (region 10, the scalars, is compared on the host, below)
+  ok = ok && state_each_array(10, h, [&](int r, DiffDev* d) {
+    const unsigned grid = state_grid(ra[r].words, 4096);
+    if (repair) hipLaunchKernelGGL(cmx_state_repair_kernel, dim3(grid), dim3(256), 0, 0, (uint32_t*)ra[r].p, rb[r].p, ra[r].words, ra[r].per_mixer, d, r == 0 ? touched : nullptr);
+    else hipLaunchKernelGGL(cmx_state_diff_kernel, dim3(grid), dim3(256), 0, 0, ra[r].p, rb[r].p, ra[r].words, ra[r].per_mixer, d);
+  });
   MixState sa, sb;
-  ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, d, sizeof(DiffDev) * 10, hipMemcpyDeviceToHost) == hipSuccess;
   if (ok && touched && h[0].cnt) {   // (behind the repair kernel on the same stream)
     hipLaunchKernelGGL(cmx_verify_reseg_kernel, dim3(2048), dim3(256), 0, 0, ra[0].p, touched, vseg, nseg);
     ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
@@ -452,7 +307,6 @@ static int state_walk(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20], bool r
   }
   out[18] = h[0].mask;
   out[19] = h[1].mask | (h[2].mask ? 1ull << CMX_MIX1 : 0);
-  if (d) (void)hipFree(d);
   if (touched) (void)hipFree(touched);
   if (!ok) { (void)hipGetLastError(); cmx_set_err(who + ": device error"); return 1; }
   return 0;
@@ -470,13 +324,7 @@ int cmx_mixnet_debug_state_xor(cmx_mixnet_t* net, int region, uint64_t mixer, ui
   const unsigned long long w = word_of(region, mixer, row, index, r);
   if (w == kNone) { cmx_set_err("cmx_mixnet_debug_state_xor: no such word (region, mixer, row, index out of range)"); return 1; }
   uint32_t* p = region < 10 ? (uint32_t*)r[region].p + w : (uint32_t*)((char*)ds + scalar_offset(w));
-  uint32_t x = 0;
-  if (hipSetDevice(dev) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&x, p, 4, hipMemcpyDeviceToHost) != hipSuccess) {
-    cmx_set_err("cmx_mixnet_debug_state_xor: device error"); return 1;
-  }
-  x ^= xor_mask;
-  if (hipMemcpy(p, &x, 4, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_mixnet_debug_state_xor: device error"); return 1; }
-  return 0;
+  return state_xor("cmx_mixnet_debug_state_xor", dev, p, xor_mask);
 }
 
 }  // extern "C"

@@ -372,19 +372,54 @@ def _shadow_repairs(fn, h):
     return {"total": v[0], "log": log}
 
 
-def _region(r):
-    return STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
+def _region(r, names=STATE_REGIONS):
+    return names.index(r) if isinstance(r, str) else int(r)
 
 
-class Vote:
-    """The vote kernel over n = 2 or 3 instances' p [T] and mixer outputs [T, 47] (CUDA float32 / int32 / uint8 tensors of 4-byte words are all
-    taken as words); the record is sticky across run() calls."""
+class _VoteBase:
+    """What the four vote wrappers share: the handle of cmx_<PREFIX>_create, report(), last(), close(). The record is sticky across run() calls."""
+    PREFIX = None
 
     def __init__(self, n, device=0):
         self.n = int(n)
-        self.h = lib().cmx_vote_create(device, self.n)
+        self.h = self._c("create")(device, self.n)
         if not self.h:
             raise CmxError(last_error())
+
+    def _c(self, name):
+        return getattr(lib(), "cmx_%s_%s" % (self.PREFIX, name))
+
+    def report(self):
+        """dict: chunks, bits, n, events (chunks with a non-agreeing element), and of the first event: first_bit, column, odd (instance, None = no
+        majority), elements; raw = the eight words. What bits and column count is the stage's (see the class). Synchronises the device."""
+        return _vote_report(self._c("report"), self.h)
+
+    def last(self):
+        """the chunk voted last alone (cmx_*vote_last): dict elements (0 = the instances agreed), bit, column, odd (None = no majority; bit, column
+        and odd are None without an event), raw = the four words. Synchronises the device."""
+        out = (C.c_uint64 * 4)()
+        if self._c("last")(self.h, out):
+            raise CmxError(last_error())
+        v = [int(x) for x in out]
+        ev = v[0] != 0
+        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._c("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Vote(_VoteBase):
+    """The vote kernel over n = 2 or 3 instances' p [T] and mixer outputs [T, 47] (CUDA float32 / int32 / uint8 tensors of 4-byte words are all
+    taken as words). In report() and last(), column = 0..46 the mixer, 47 the final p."""
+    PREFIX = "vote"
 
     def run(self, ps, mixes, stream_bit0=0, sel=None, bits=None, stream=None):
         import torch
@@ -401,45 +436,15 @@ class Vote:
                               bits.data_ptr() if bits is not None else None, C.c_void_p(stream)):
             raise CmxError(last_error())
 
-    def report(self):
-        """dict: chunks, bits, n, events (chunks with a non-agreeing element), and of the first event: first_bit, column (0..46 mixer, 47 final p),
-        odd (instance, None = no majority), elements; raw = the eight words. Synchronises the device."""
-        return _vote_report(lib().cmx_vote_report, self.h)
-
-    def last(self):
-        """the chunk voted last alone (cmx_vote_last): dict elements (0 = the instances agreed), bit, column, odd (None = no majority; bit, column
-        and odd are None without an event), raw = the four words. Synchronises the device."""
-        out = (C.c_uint64 * 4)()
-        if lib().cmx_vote_last(self.h, out):
-            raise CmxError(last_error())
-        v = [int(x) for x in out]
-        ev = v[0] != 0
-        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
-
     def values(self):
         """the captured bit of the first event: words [n, 48] u32, sel [47] u32, bit"""
         return _vote_values(lib().cmx_vote_values, self.h, self.n)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().cmx_vote_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # the redundant context-stage vote (include/cmix_amd.h, cmx_ctxvote_*; the rule's specification is cmix_amd.ctxvote.ctx_vote_reference)
 CTX_STATE_REGIONS = ("persist", "history", "shared_map", "bstack", "pred", "cnt", "chk", "match_map", "ihash")
 CTXVOTE_COLS = 101   # CMX_CTXVOTE_COLS: 54 model outputs in lane order (layer-0 columns SMALL_COLS), then the 47 selectors
 CTX_COMPACT_STRIDE = 64
-
-
-def _ctx_region(r):
-    return CTX_STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
 
 
 def _ctx_vote_values(fn, h, n):
@@ -463,15 +468,11 @@ def ctx_layout():
     return dict(zip(("regs", "br_probs", "ipred", "mpred", "words"), [int(x) for x in out]))
 
 
-class CtxVote:
+class CtxVote(_VoteBase):
     """The context-stage vote kernel over n = 2 or 3 instances' model outputs (a CUDA [T, stride] matrix of 4-byte words: stride >= 2078 the full
-    layer-0 form, compact=True the [T, >= 64] form) and selectors [T, 47]; the record is sticky across run() calls."""
-
-    def __init__(self, n, device=0):
-        self.n = int(n)
-        self.h = lib().cmx_ctxvote_create(device, self.n)
-        if not self.h:
-            raise CmxError(last_error())
+    layer-0 form, compact=True the [T, >= 64] form) and selectors [T, 47]; the record is sticky across run() calls. In report() and
+    last(), column = the element's c (0..53 model output in lane order, 54..100 selector c - 54)."""
+    PREFIX = "ctxvote"
 
     def run(self, probs, compact, sels, stream_bit0=0, bits=None, stream=None):
         import torch
@@ -489,33 +490,9 @@ class CtxVote:
         if lib().cmx_ctxvote_run(self.h, ap, ast, ac, asel, T, int(stream_bit0), bits.data_ptr() if bits is not None else None, C.c_void_p(stream)):
             raise CmxError(last_error())
 
-    def report(self):
-        """as Vote.report; column = the element's c (0..53 model output in lane order, 54..100 selector c - 54). Synchronises the device."""
-        return _vote_report(lib().cmx_ctxvote_report, self.h)
-
-    def last(self):
-        """as Vote.last"""
-        out = (C.c_uint64 * 4)()
-        if lib().cmx_ctxvote_last(self.h, out):
-            raise CmxError(last_error())
-        v = [int(x) for x in out]
-        ev = v[0] != 0
-        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
-
     def values(self):
         """the captured bit of the first event: words [n, 101] u32, bit"""
         return _ctx_vote_values(lib().cmx_ctxvote_values, self.h, self.n)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().cmx_ctxvote_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # the redundant LSTM-stage vote (include/cmix_amd.h, cmx_lstmvote_*; the rule's specification is cmix_amd.lstmvote.lstm_vote_reference)
@@ -527,10 +504,6 @@ LSTM_STATE_ARRAYS = tuple(["%s[%d][%d]" % (a, l, g) for a in ("W", "WT", "M", "V
                           ["%s[%d]" % (a, l) for a in ("last_state", "tanh_state", "in_gate_state") for l in range(2)] +
                           ["stateb[0][0]", "stateb[0][1]", "stateb[1][0]", "stateb[1][1]", "hid[0]", "hid[1]", "layer_input[0]", "layer_input[1]", "OL", "output",
                            "input_history", "bp_symbol", "dyn", "byte_probs", "d_prev_probs", "raw_ring", "h_ring", "logit_ring", "bp_pub"])
-
-
-def _lstm_region(r):
-    return LSTM_STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
 
 
 def _lstm_vote_values(fn, h, n):
@@ -556,15 +529,12 @@ def lstm_layout(lstm):
     return [{"name": LSTM_STATE_ARRAYS[i], "region": LSTM_STATE_REGIONS[int(out[3 * i])], "offset": int(out[3 * i + 1]), "words": int(out[3 * i + 2])} for i in range(n)]
 
 
-class LstmVote:
+class LstmVote(_VoteBase):
     """The LSTM-stage vote kernel over n = 2 or 3 instances' distributions [N, 256], bit predictions and ex [N, 8] (CUDA tensors of 4-byte words); an
-    instance's bit predictions may instead be a [8N, 2078] layer-0 matrix, read in place from its column 2077. The record is sticky across run()."""
-
-    def __init__(self, n, device=0):
-        self.n = int(n)
-        self.h = lib().cmx_lstmvote_create(device, self.n)
-        if not self.h:
-            raise CmxError(last_error())
+    instance's bit predictions may instead be a [8N, 2078] layer-0 matrix, read in place from its column 2077. In report() and last(), bytes stand
+    for bits: bits = bytes voted, first_bit / bit = the stream byte, column = the element's c (0..255 distribution entry, 256..263 bit prediction,
+    264..271 ex)."""
+    PREFIX = "lstmvote"
 
     def run(self, dists, bit_ps, exs, stream_byte0=0, data=None, stream=None):
         import torch
@@ -590,34 +560,9 @@ class LstmVote:
         if lib().cmx_lstmvote_run(self.h, ad, ap, ast, ax, N, int(stream_byte0), data.data_ptr() if data is not None else None, C.c_void_p(stream)):
             raise CmxError(last_error())
 
-    def report(self):
-        """as Vote.report with bytes for bits: bits = bytes voted, first_bit = the first event's stream byte, column = the element's c (0..255
-        distribution entry, 256..263 bit prediction, 264..271 ex). Synchronises the device."""
-        return _vote_report(lib().cmx_lstmvote_report, self.h)
-
-    def last(self):
-        """as Vote.last (bit = the stream byte)"""
-        out = (C.c_uint64 * 4)()
-        if lib().cmx_lstmvote_last(self.h, out):
-            raise CmxError(last_error())
-        v = [int(x) for x in out]
-        ev = v[0] != 0
-        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
-
     def values(self):
         """the captured row of the first event: words [n, 272] u32, byte"""
         return _lstm_vote_values(lib().cmx_lstmvote_values, self.h, self.n)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().cmx_lstmvote_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # the redundant fxcm-stage vote (include/cmix_amd.h, cmx_fxcmvote_*; the rule's specification is cmix_amd.fxcmvote.fxcm_vote_reference)
@@ -628,10 +573,6 @@ FXCM_STATE_ARRAYS = tuple(["squash", "stretch", "wrt"] + ["sta[%d]" % i for i in
                           ["maps[%d].t" % k for k in range(31)] + ["maps[%d].sm" % k for k in range(31)] + ["sscm_data[%d]" % j for j in range(7)] +
                           ["sm1_t[%d]" % j for j in range(3)] + ["rcm_t", "mhash", "sp_table", "buffer"] + ["wx[%d]" % k for k in range(12)] +
                           ["apm_t[%d]" % j for j in range(6)] + ["FxDev"])
-
-
-def _fxcm_region(r):
-    return FXCM_STATE_REGIONS.index(r) if isinstance(r, str) else int(r)
 
 
 def _fxcm_vote_values(fn, h, n):
@@ -657,16 +598,11 @@ def fxcm_layout(fx):
     return [{"name": FXCM_STATE_ARRAYS[i], "region": FXCM_STATE_REGIONS[int(out[3 * i])], "offset": int(out[3 * i + 1]), "words": int(out[3 * i + 2])} for i in range(n)]
 
 
-class FxcmVote:
+class FxcmVote(_VoteBase):
     """The fxcm-stage vote kernel over n = 2 or 3 instances' rows (CUDA float32 / 4-byte-word tensors [T, stride]): a [T, 2078] layer-0 matrix is read in
     place from its columns 3..433, a [T, 434] matrix (what Fxcm.run_shared writes) from columns 3..433 as well, a [T, 431] matrix as it is. The record is
-    sticky across run()."""
-
-    def __init__(self, n, device=0):
-        self.n = int(n)
-        self.h = lib().cmx_fxcmvote_create(device, self.n)
-        if not self.h:
-            raise CmxError(last_error())
+    sticky across run(). In report() and last(), column = the fxcm column c (layer-0 column 3 + c)."""
+    PREFIX = "fxcmvote"
 
     def run(self, rows, stream_bit0=0, data=None, stream=None):
         import torch
@@ -684,33 +620,9 @@ class FxcmVote:
         if lib().cmx_fxcmvote_run(self.h, ap, ast, T, int(stream_bit0), data.data_ptr() if data is not None else None, C.c_void_p(stream)):
             raise CmxError(last_error())
 
-    def report(self):
-        """as Vote.report: bits voted, first_bit = the first event's stream bit, column = the fxcm column c (layer-0 column 3 + c). Synchronises."""
-        return _vote_report(lib().cmx_fxcmvote_report, self.h)
-
-    def last(self):
-        """as Vote.last"""
-        out = (C.c_uint64 * 4)()
-        if lib().cmx_fxcmvote_last(self.h, out):
-            raise CmxError(last_error())
-        v = [int(x) for x in out]
-        ev = v[0] != 0
-        return {"elements": v[0], "bit": v[1] if ev else None, "column": v[2] if ev else None, "odd": _opt(v[3]) if ev else None, "raw": v}
-
     def values(self):
         """the captured row of the first event: words [n, 431] u32, the bit coded there and its byte"""
         return _fxcm_vote_values(lib().cmx_fxcmvote_values, self.h, self.n)
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().cmx_fxcmvote_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def probe_libm(which, x, device=0):
@@ -1017,7 +929,7 @@ class Lstm:
 
     def debug_state_xor(self, region, index, xor_mask):
         """Test hook: XOR one state word (region: number or LSTM_STATE_REGIONS name) between runs; the index region is refused."""
-        if lib().cmx_lstm_debug_state_xor(self.h, _lstm_region(region), int(index), int(xor_mask)):
+        if lib().cmx_lstm_debug_state_xor(self.h, _region(region, LSTM_STATE_REGIONS), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def gate_weights(self, layer, gate):
@@ -1053,7 +965,7 @@ class CtxModels:
 
     def debug_state_xor(self, region, lane, index, xor_mask):
         """Test hook: XOR one state word (region: number or CTX_STATE_REGIONS name; lane None in regions 0..3), between chunks."""
-        if lib().cmx_ctxmodels_debug_state_xor(self.h, _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
+        if lib().cmx_ctxmodels_debug_state_xor(self.h, _region(region, CTX_STATE_REGIONS), _u64(lane), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def close(self):
@@ -1356,7 +1268,7 @@ class Pipeline:
 
     def debug_ctx_shadow_xor(self, instance, region, lane, index, xor_mask):
         """Test hook: CtxModels.debug_state_xor on one instance, between chunks."""
-        if lib().cmx_pipeline_debug_ctx_shadow_xor(self.h, int(instance), _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
+        if lib().cmx_pipeline_debug_ctx_shadow_xor(self.h, int(instance), _region(region, CTX_STATE_REGIONS), _u64(lane), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def set_lstm_shadow(self, k):
@@ -1383,7 +1295,7 @@ class Pipeline:
 
     def debug_lstm_shadow_xor(self, instance, region, index, xor_mask):
         """Test hook: Lstm.debug_state_xor on one instance, between chunks."""
-        if lib().cmx_pipeline_debug_lstm_shadow_xor(self.h, int(instance), _lstm_region(region), int(index), int(xor_mask)):
+        if lib().cmx_pipeline_debug_lstm_shadow_xor(self.h, int(instance), _region(region, LSTM_STATE_REGIONS), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def set_fxcm_shadow(self, k):
@@ -1410,7 +1322,7 @@ class Pipeline:
 
     def debug_fxcm_shadow_xor(self, instance, region, index, xor_mask):
         """Test hook: Fxcm.debug_state_xor on one instance, between chunks."""
-        if lib().cmx_pipeline_debug_fxcm_shadow_xor(self.h, int(instance), _fxcm_region(region), int(index), int(xor_mask)):
+        if lib().cmx_pipeline_debug_fxcm_shadow_xor(self.h, int(instance), _region(region, FXCM_STATE_REGIONS), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def mixnet_mode(self):
@@ -1714,7 +1626,7 @@ class Predictor:
 
     def debug_ctx_shadow_xor(self, after_chunk, instance, region, lane, index, xor_mask):
         """Test hook: one Pipeline.debug_ctx_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""
-        if lib().cmx_debug_ctx_shadow_xor(self.h, int(after_chunk), int(instance), _ctx_region(region), _u64(lane), int(index), int(xor_mask)):
+        if lib().cmx_debug_ctx_shadow_xor(self.h, int(after_chunk), int(instance), _region(region, CTX_STATE_REGIONS), _u64(lane), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def set_journal(self, log2=19):
@@ -1811,13 +1723,13 @@ class Fxcm:
     def debug_state_read(self, region, index, count):
         """Test readout: `count` words of a region from `index` on, as uint32 (cmx_fxcm_debug_state_read). Synchronises."""
         out = np.zeros(int(count), np.uint32)
-        if lib().cmx_fxcm_debug_state_read(self.h, _fxcm_region(region), int(index), int(count), out.ctypes.data):
+        if lib().cmx_fxcm_debug_state_read(self.h, _region(region, FXCM_STATE_REGIONS), int(index), int(count), out.ctypes.data):
             raise CmxError(last_error())
         return out
 
     def debug_state_xor(self, region, index, xor_mask):
         """Test hook: XOR one state word (region: number or FXCM_STATE_REGIONS name) between launches; regions whose words address memory are refused."""
-        if lib().cmx_fxcm_debug_state_xor(self.h, _fxcm_region(region), int(index), int(xor_mask)):
+        if lib().cmx_fxcm_debug_state_xor(self.h, _region(region, FXCM_STATE_REGIONS), int(index), int(xor_mask)):
             raise CmxError(last_error())
 
     def close(self):

@@ -7,23 +7,17 @@ column 3 + c; "first" is the lowest bit, then the lowest column. n = 3: all equa
 different is no majority; n = 2: different is no majority."""
 import numpy as np
 
-NONE = (1 << 64) - 1   # "no majority" in field [6]
+from .votecore import NONE, VoteTwin, chunk_rule, vote_rule, words  # noqa: F401 (NONE is this module's too)
+
 COLS = 431
 FIRST_COL = 3          # of the 431 in a layer-0 row or in a shadow's dense row
 LAYER0_STRIDE, SHADOW_STRIDE = 2078, 434
 
 
-def _words(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype.itemsize != 4:
-        raise ValueError("fxcm_vote_reference: arrays of 4-byte words")
-    return a.view(np.uint32)
-
-
 def rows_of(r):
     """the [T, 431] words of an instance: a [T, 431] array as it is, or columns 3..433 of a wider one ([T, 2078] layer-0 rows read in place, [T, 434]
     a shadow's dense rows)"""
-    w = _words(r)
+    w = words(r, "fxcm_vote_reference")
     if w.ndim != 2 or w.shape[1] < COLS:
         raise ValueError("fxcm_vote_reference: rows of at least 431 words")
     return w if w.shape[1] == COLS else w[:, FIRST_COL:FIRST_COL + COLS]
@@ -43,81 +37,19 @@ def _stack(rows):
     return np.stack(w)
 
 
-def _differ(w):
-    differ = (w != w[0]).any(axis=0)
-    if w.shape[0] == 3:
-        differ |= w[1] != w[2]
-    return differ
-
-
 def fxcm_vote_reference(rows, stream_bit0=0):
-    """rows: n arrays of T rows (see rows_of). Returns (record, words): record = the eight fields one cmx_fxcmvote_run call on a fresh handle leaves --
-    [0] chunks (1), [1] bits, [2] n, [3] 1 if any element does not agree, then [4] the stream bit of the smallest non-agreeing e, [5] its c, [6] the
-    odd instance there or NONE, [7] the non-agreeing elements (0 in [4..7] without an event) -- and words = the captured [n, 431] uint32 words of that
-    bit (None without an event)."""
-    w = _stack(rows)
-    n, T = w.shape[0], w.shape[1]
-    differ = _differ(w)
-    rec = [1, T, n, 0, 0, 0, 0, 0]
-    if not differ.any():
-        return rec, None
-    e = int(np.flatnonzero(differ.reshape(-1))[0])
-    t, c = divmod(e, COLS)
-    v = [int(w[i, t, c]) for i in range(n)]
-    odd = NONE
-    if n == 3:
-        if v[1] == v[2]:
-            odd = 0
-        elif v[0] == v[2]:
-            odd = 1
-        elif v[0] == v[1]:
-            odd = 2
-    rec[3:] = [1, stream_bit0 + t, c, odd, int(differ.sum())]
-    return rec, w[:, t, :].copy()
+    """rows: n arrays of T rows (see rows_of). Returns (record, words) as votecore.vote_rule: the eight fields one cmx_fxcmvote_run call on a fresh
+    handle leaves ([1] bits, [4] the stream bit, [5] the fxcm column c) and the captured [n, 431] uint32 words of that bit."""
+    return vote_rule(_stack(rows), stream_bit0)
 
 
 def chunk_result(rows, stream_bit0=0):
-    """The chunk's own result as cmx_fxcmvote_last reports it: [elements, stream bit, c, odd]. odd is the ONE instance that is odd at every
-    non-agreeing element, else NONE (an element at which all differ, two instances, or elements with different odd instances)."""
-    rec, _ = fxcm_vote_reference(rows, stream_bit0)
-    if not rec[3]:
-        return [0, 0, 0, 0]
-    w = _stack(rows)
-    odd = set()
-    if w.shape[0] == 2:
-        odd.add(NONE)
-    else:
-        a, b, c = w[0] == w[1], w[1] == w[2], w[0] == w[2]
-        if (b & ~a).any():
-            odd.add(0)
-        if (c & ~a).any():
-            odd.add(1)
-        if (a & ~b).any():
-            odd.add(2)
-        if (~a & ~b & ~c).any():
-            odd.add(NONE)
-    return [rec[7], rec[4], rec[5], odd.pop() if len(odd) == 1 else NONE]
+    """The chunk's own result as cmx_fxcmvote_last reports it: [elements, stream bit, c, odd] (votecore.chunk_rule)."""
+    return chunk_rule(_stack(rows), stream_bit0)
 
 
-class FxcmVoteTwin:
-    """The sticky record over several chunks, as a cmx_fxcmvote_t keeps it: run() folds one chunk; record [8], last [4], words (the first event's row)."""
-
-    def __init__(self, n):
-        self.n = int(n)
-        self.record = [0, 0, self.n, 0, 0, 0, 0, 0]
-        self.last = [0, 0, 0, 0]
-        self.words = None
+class FxcmVoteTwin(VoteTwin):
+    """votecore.VoteTwin over the fxcm stage's rows, as a cmx_fxcmvote_t keeps its record"""
 
     def run(self, rows, stream_bit0=0):
-        if len(rows) != self.n:
-            raise ValueError("FxcmVoteTwin.run: %d instances" % self.n)
-        rec, words = fxcm_vote_reference(rows, stream_bit0)
-        self.last = chunk_result(rows, stream_bit0)
-        self.record[0] += 1
-        self.record[1] += rec[1]
-        if rec[3]:
-            if not self.record[3]:
-                self.record[4:] = rec[4:]
-                self.words = words
-            self.record[3] += 1
-        return self.last
+        return VoteTwin.run(self, _stack(rows), stream_bit0)
