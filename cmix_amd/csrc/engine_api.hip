@@ -42,6 +42,7 @@
 
 #include "../../include/cmix_amd.h"
 #include "cmx_journal.h"
+#include "cmx_shadow_text.h"
 #include "cmx_streams.h"
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
@@ -77,19 +78,21 @@ struct LookAhead {                            // the handle in look-ahead mode (
 };
 }  // namespace
 
+// the pipeline's entry points of the four kinds of shadow stages, in ShadowId's order
+static int (*const kPipeSetShadow[SH_KINDS])(cmx_pipeline_t*, int) = {cmx_pipeline_set_shadow, cmx_pipeline_set_ctx_shadow, cmx_pipeline_set_lstm_shadow, cmx_pipeline_set_fxcm_shadow};
+static int (*const kPipeShadowReport[SH_KINDS])(cmx_pipeline_t*, uint64_t*) = {cmx_pipeline_shadow_report, cmx_pipeline_ctx_shadow_report, cmx_pipeline_lstm_shadow_report,
+                                                                               cmx_pipeline_fxcm_shadow_report};
+
 struct cmx_engine {
   int device = 0;
   uint8_t vocab[256];
   std::string dict;               // the hidden global `dictionary_path` (runner.cpp:17), read by the fxcm stage
   bool has_dict = false;
   bool verify = false;            // cmx_set_verify: the look-ahead pipeline's mixing network runs in verify mode
-  int shadow = 0;                 // cmx_set_shadow: shadow mixing networks of the look-ahead pipeline, voting on every chunk
+  int shadow[SH_KINDS] = {};      // cmx_set_shadow, _ctx_shadow, _lstm_shadow, _fxcm_shadow: shadow stages of the look-ahead pipeline, voting on every chunk
   int shadow_repair = 0;          // cmx_set_shadow_repair: repairs on the majority the pipeline may make (0 = off)
-  struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t mixer = 0, row = 0, index = 0; uint32_t mask = 0; } dbg_xor;   // cmx_debug_shadow_xor
-  int ctx_shadow = 0;             // cmx_set_ctx_shadow: shadow context stages of the look-ahead pipeline, voting on every chunk
-  struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t lane = 0, index = 0; uint32_t mask = 0; } dbg_cxor;   // cmx_debug_ctx_shadow_xor
-  int lstm_shadow = 0;            // cmx_set_lstm_shadow: shadow LSTM stages of the look-ahead pipeline, voting on every chunk
-  int fxcm_shadow = 0;            // cmx_set_fxcm_shadow: shadow fxcm stages of the look-ahead pipeline, voting on every chunk
+  // cmx_debug_shadow_xor / cmx_debug_ctx_shadow_xor (by ShadowId): one armed flip, a = the mixer and b the row, or a = the lane
+  struct { bool armed = false; uint64_t after = 0; int instance = 0, region = 0; uint64_t a = 0, b = 0, index = 0; uint32_t mask = 0; } dbg_xor[2];
   int journal = 0;                // cmx_set_journal: log2 of the stream journal's block (0 = off): the look-ahead pipeline's kernel, or a decoder's host-side fold
   CmxHostJournal* hj = nullptr;   // a decoder's journal (mode 3): the p and bits words, folded on this thread bit by bit
   std::vector<std::array<uint64_t, 3>> jr_want; bool jr_check = false;   // cmx_set_journal_check: a compressor's journal to hold the decode to
@@ -339,13 +342,12 @@ int ensure_lookahead(cmx_engine* h) {
   h->la = la;
   la->pipe = cmx_pipeline_create(h->vocab, h->device, kLaChunk);
   bool ok = la->pipe && cmx_pipeline_enable_fxcm(la->pipe, h->has_dict ? h->dict.c_str() : nullptr) == 0 &&
-            cmx_pipeline_enable_paq8(la->pipe) == 0 && (!h->verify || cmx_pipeline_set_verify(la->pipe, 1) == 0) &&
-            (!h->shadow || cmx_pipeline_set_shadow(la->pipe, h->shadow) == 0) &&
-            (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0) &&
-            (!h->ctx_shadow || cmx_pipeline_set_ctx_shadow(la->pipe, h->ctx_shadow) == 0) &&   // (before the pretraining below: every instance learns the dictionary)
-            (!h->lstm_shadow || cmx_pipeline_set_lstm_shadow(la->pipe, h->lstm_shadow) == 0) &&
-            (!h->fxcm_shadow || cmx_pipeline_set_fxcm_shadow(la->pipe, h->fxcm_shadow) == 0) &&   // (before the pretraining below as well: fxcm learns the dictionary)
-            (!h->journal || cmx_pipeline_set_journal(la->pipe, h->journal) == 0);
+            cmx_pipeline_enable_paq8(la->pipe) == 0 && (!h->verify || cmx_pipeline_set_verify(la->pipe, 1) == 0);
+  for (int k = 0; ok && k < SH_KINDS; ++k) {   // (before the pretraining below: every context-stage and fxcm instance learns the dictionary)
+    ok = !h->shadow[k] || kPipeSetShadow[k](la->pipe, h->shadow[k]) == 0;
+    if (k == SH_MIX) ok = ok && (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0);
+  }
+  ok = ok && (!h->journal || cmx_pipeline_set_journal(la->pipe, h->journal) == 0);
   if (ok && h->jr_check) { cmx_set_err("cmx_stage_input: a journal to check against is set (cmx_set_journal_check), which covers a decoder only"); ok = false; }
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
   const size_t T = 8 * kLaChunk;
@@ -374,13 +376,12 @@ int la_top_up(cmx_engine* h, bool force_tail) {
     if (n > kLaChunk) n = kLaChunk;
     else if (n < kLaChunk && !la->ended && !force_tail) break;
     const size_t k = la->n_sub % kLaSlots;
-    if (h->dbg_xor.armed && la->n_sub == h->dbg_xor.after + 1) {   // (test hook) between chunk `after` and this one
-      h->dbg_xor.armed = false;
-      if (cmx_pipeline_debug_shadow_xor(la->pipe, h->dbg_xor.instance, h->dbg_xor.region, h->dbg_xor.mixer, h->dbg_xor.row, h->dbg_xor.index, h->dbg_xor.mask)) return 1;
-    }
-    if (h->dbg_cxor.armed && la->n_sub == h->dbg_cxor.after + 1) {   // (test hook) the same for a context-stage instance
-      h->dbg_cxor.armed = false;
-      if (cmx_pipeline_debug_ctx_shadow_xor(la->pipe, h->dbg_cxor.instance, h->dbg_cxor.region, h->dbg_cxor.lane, h->dbg_cxor.index, h->dbg_cxor.mask)) return 1;
+    for (int x = 0; x < 2; ++x) {   // (test hooks) between chunk `after` and this one
+      auto& d = h->dbg_xor[x];
+      if (!d.armed || la->n_sub != d.after + 1) continue;
+      d.armed = false;
+      if (x == SH_MIX ? cmx_pipeline_debug_shadow_xor(la->pipe, d.instance, d.region, d.a, d.b, d.index, d.mask)
+                      : cmx_pipeline_debug_ctx_shadow_xor(la->pipe, d.instance, d.region, d.a, d.index, d.mask)) return 1;
     }
     if (cmx_pipeline_submit(la->pipe, la->data.data() + (la->submitted - la->base), n, la->d_layer0[k], la->d_p[k])) return 1;
     la->ring[k].off = la->submitted;
@@ -710,20 +711,34 @@ int cmx_verify_report(cmx_t* h, uint64_t out[8]) {
   return cmx_pipeline_verify_report(h->la->pipe, out);
 }
 
-// shadow mixing networks of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
-int cmx_set_shadow(cmx_t* h, int k) {
-  if (!h) { cmx_set_err("cmx_set_shadow: null handle"); return 1; }
-  if (k < 0 || k > 2) { cmx_set_err("cmx_set_shadow: k must be 0, 1 or 2 shadow mixing networks"); return 1; }
-  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
-  if (k != 2 && h->shadow_repair) { cmx_set_err("cmx_set_shadow: repair on the majority is set (cmx_set_shadow_repair), which needs 2 shadows"); return 1; }
-  h->shadow = k;
+// shadow stages of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
+static int set_shadow(cmx_engine* h, int kind, int k) {
+  const std::string fn = shadow_fn(kind, "cmx_set_", "");
+  if (!h) { cmx_set_err(fn + ": null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err(fn + ": k must be 0, 1 or 2 " + shadow_words(kind).noun + "s"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err(fn + ": only before the first cmx_stage_input / cmx_predict"); return 1; }
+  if (kind == SH_MIX && k != 2 && h->shadow_repair) { cmx_set_err(fn + ": repair on the majority is set (cmx_set_shadow_repair), which needs 2 shadows"); return 1; }
+  h->shadow[kind] = k;
   return 0;
 }
+int cmx_set_shadow(cmx_t* h, int k) { return set_shadow(h, SH_MIX, k); }
+int cmx_set_ctx_shadow(cmx_t* h, int k) { return set_shadow(h, SH_CTX, k); }
+int cmx_set_lstm_shadow(cmx_t* h, int k) { return set_shadow(h, SH_LSTM, k); }
+int cmx_set_fxcm_shadow(cmx_t* h, int k) { return set_shadow(h, SH_FXCM, k); }
+static int shadow_report(cmx_engine* h, int kind, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err(shadow_fn(kind, "cmx_", "_report") + ": bad argument"); return 1; }
+  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
+  return kPipeShadowReport[kind](h->la->pipe, out);
+}
+int cmx_shadow_report(cmx_t* h, uint64_t out[8]) { return shadow_report(h, SH_MIX, out); }
+int cmx_ctx_shadow_report(cmx_t* h, uint64_t out[8]) { return shadow_report(h, SH_CTX, out); }
+int cmx_lstm_shadow_report(cmx_t* h, uint64_t out[8]) { return shadow_report(h, SH_LSTM, out); }
+int cmx_fxcm_shadow_report(cmx_t* h, uint64_t out[8]) { return shadow_report(h, SH_FXCM, out); }
 int cmx_set_shadow_repair(cmx_t* h, int max_repairs) {
   if (!h) { cmx_set_err("cmx_set_shadow_repair: null handle"); return 1; }
   if (max_repairs < 0) { cmx_set_err("cmx_set_shadow_repair: max_repairs must be 0 (off) or the number of repairs allowed"); return 1; }
   if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_shadow_repair: only before the first cmx_stage_input / cmx_predict"); return 1; }
-  if (max_repairs && h->shadow != 2) { cmx_set_err("cmx_set_shadow_repair: repair needs 2 shadow mixing networks (cmx_set_shadow(h, 2) first): a vote of two has no majority"); return 1; }
+  if (max_repairs && h->shadow[SH_MIX] != 2) { cmx_set_err("cmx_set_shadow_repair: repair needs 2 shadow mixing networks (cmx_set_shadow(h, 2) first): a vote of two has no majority"); return 1; }
   h->shadow_repair = max_repairs;
   return 0;
 }
@@ -732,18 +747,21 @@ int cmx_shadow_repairs(cmx_t* h, uint64_t out[], size_t cap) {
   if (!h->la) { out[0] = out[1] = 0; return 0; }
   return cmx_pipeline_shadow_repairs(h->la->pipe, out, cap);
 }
-int cmx_debug_shadow_xor(cmx_t* h, uint64_t after_chunk, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
-  if (!h) { cmx_set_err("cmx_debug_shadow_xor: null handle"); return 1; }
-  if (!h->shadow) { cmx_set_err("cmx_debug_shadow_xor: no shadow mixing networks are set"); return 1; }
-  if (h->la && h->la->n_sub > after_chunk + 1) { cmx_set_err("cmx_debug_shadow_xor: that chunk has been submitted already"); return 1; }
-  h->dbg_xor.armed = true; h->dbg_xor.after = after_chunk; h->dbg_xor.instance = instance; h->dbg_xor.region = region;
-  h->dbg_xor.mixer = mixer; h->dbg_xor.row = row; h->dbg_xor.index = index; h->dbg_xor.mask = xor_mask;
+// TEST HOOKS: arm one flip in an instance's state, made between chunk `after_chunk` and the next (la_top_up)
+static int arm_xor(cmx_engine* h, int kind, uint64_t after_chunk, int instance, int region, uint64_t a, uint64_t b, uint64_t index, uint32_t xor_mask) {
+  const std::string fn = shadow_fn(kind, "cmx_debug_", "_xor");
+  if (!h) { cmx_set_err(fn + ": null handle"); return 1; }
+  if (!h->shadow[kind]) { cmx_set_err(fn + ": no " + shadow_words(kind).noun + "s are set"); return 1; }
+  if (h->la && h->la->n_sub > after_chunk + 1) { cmx_set_err(fn + ": that chunk has been submitted already"); return 1; }
+  auto& d = h->dbg_xor[kind];
+  d.armed = true; d.after = after_chunk; d.instance = instance; d.region = region; d.a = a; d.b = b; d.index = index; d.mask = xor_mask;
   return 0;
 }
-int cmx_shadow_report(cmx_t* h, uint64_t out[8]) {
-  if (!h || !out) { cmx_set_err("cmx_shadow_report: bad argument"); return 1; }
-  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
-  return cmx_pipeline_shadow_report(h->la->pipe, out);
+int cmx_debug_shadow_xor(cmx_t* h, uint64_t after_chunk, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
+  return arm_xor(h, SH_MIX, after_chunk, instance, region, mixer, row, index, xor_mask);
+}
+int cmx_debug_ctx_shadow_xor(cmx_t* h, uint64_t after_chunk, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask) {
+  return arm_xor(h, SH_CTX, after_chunk, instance, region, lane, 0, index, xor_mask);
 }
 
 // ---- the stream journal of a cmx_t (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict ----
@@ -809,54 +827,6 @@ int cmx_journal_close_files(cmx_t* h) {
   if (journal_write(h, nullptr, true, "cmx_journal_close_files")) return 1;
   std::string err;
   if (h->hj && cmx_hostjournal_check_tail(h->hj, &err)) { cmx_set_err("cmx_journal_close_files: " + err); return 1; }
-  return 0;
-}
-
-// shadow context stages of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
-int cmx_set_ctx_shadow(cmx_t* h, int k) {
-  if (!h) { cmx_set_err("cmx_set_ctx_shadow: null handle"); return 1; }
-  if (k < 0 || k > 2) { cmx_set_err("cmx_set_ctx_shadow: k must be 0, 1 or 2 shadow context stages"); return 1; }
-  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_ctx_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
-  h->ctx_shadow = k;
-  return 0;
-}
-int cmx_ctx_shadow_report(cmx_t* h, uint64_t out[8]) {
-  if (!h || !out) { cmx_set_err("cmx_ctx_shadow_report: bad argument"); return 1; }
-  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
-  return cmx_pipeline_ctx_shadow_report(h->la->pipe, out);
-}
-// shadow LSTM stages of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
-int cmx_set_lstm_shadow(cmx_t* h, int k) {
-  if (!h) { cmx_set_err("cmx_set_lstm_shadow: null handle"); return 1; }
-  if (k < 0 || k > 2) { cmx_set_err("cmx_set_lstm_shadow: k must be 0, 1 or 2 shadow LSTM stages"); return 1; }
-  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_lstm_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
-  h->lstm_shadow = k;
-  return 0;
-}
-// shadow fxcm stages of the look-ahead pipeline (include/cmix_amd.h): before the first cmx_stage_input / cmx_predict
-int cmx_set_fxcm_shadow(cmx_t* h, int k) {
-  if (!h) { cmx_set_err("cmx_set_fxcm_shadow: null handle"); return 1; }
-  if (k < 0 || k > 2) { cmx_set_err("cmx_set_fxcm_shadow: k must be 0, 1 or 2 shadow fxcm stages"); return 1; }
-  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_fxcm_shadow: only before the first cmx_stage_input / cmx_predict"); return 1; }
-  h->fxcm_shadow = k;
-  return 0;
-}
-int cmx_fxcm_shadow_report(cmx_t* h, uint64_t out[8]) {
-  if (!h || !out) { cmx_set_err("cmx_fxcm_shadow_report: bad argument"); return 1; }
-  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
-  return cmx_pipeline_fxcm_shadow_report(h->la->pipe, out);
-}
-int cmx_lstm_shadow_report(cmx_t* h, uint64_t out[8]) {
-  if (!h || !out) { cmx_set_err("cmx_lstm_shadow_report: bad argument"); return 1; }
-  if (h->mode != 2 || !h->la) { for (int i = 0; i < 8; ++i) out[i] = 0; return 0; }   // (nothing voted: not a compressor's handle, or nothing staged yet)
-  return cmx_pipeline_lstm_shadow_report(h->la->pipe, out);
-}
-int cmx_debug_ctx_shadow_xor(cmx_t* h, uint64_t after_chunk, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask) {
-  if (!h) { cmx_set_err("cmx_debug_ctx_shadow_xor: null handle"); return 1; }
-  if (!h->ctx_shadow) { cmx_set_err("cmx_debug_ctx_shadow_xor: no shadow context stages are set"); return 1; }
-  if (h->la && h->la->n_sub > after_chunk + 1) { cmx_set_err("cmx_debug_ctx_shadow_xor: that chunk has been submitted already"); return 1; }
-  h->dbg_cxor.armed = true; h->dbg_cxor.after = after_chunk; h->dbg_cxor.instance = instance; h->dbg_cxor.region = region;
-  h->dbg_cxor.lane = lane; h->dbg_cxor.index = index; h->dbg_cxor.mask = xor_mask;
   return 0;
 }
 

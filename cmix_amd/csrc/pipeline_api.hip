@@ -15,6 +15,7 @@
 // them inside d_layer0. No CPU fallback exists for any device stage.
 #include <hip/hip_runtime.h>
 #include <chrono>
+#include <initializer_list>
 #include <stdio.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -29,6 +30,7 @@
 #include "cmx_journal.h"
 #include "cmx_late.h"
 #include "cmx_streams.h"
+#include "pipeline_shadow.h"
 
 extern "C" int cmx_p8stage_streams(cmx_p8stage_t* h, hipStream_t* out, int cap);   // p8stage.hip: the role streams
 
@@ -128,31 +130,9 @@ struct Slot {
   hipEvent_t ev_p80 = nullptr, ev_p81 = nullptr;   // paq8 stage (opt-in)
   bool used = false;
   bool untimed = false;  // the chunk in this slot has not been added to the stage totals yet
-  // shadow mixing networks (cmx_pipeline_set_shadow): allocated at the first finish, nothing of it otherwise
-  float* d_shp[2] = {nullptr, nullptr};               // [8 max] p of shadow i + 1
-  float* d_shmix[3] = {nullptr, nullptr, nullptr};    // [8 max][47] mixer outputs of instance i (0: the stream's own network, unless cmx_pipeline_debug_mix_out supplies the area)
-  unsigned long long* h_vote = nullptr;               // pinned [8] the vote's record as it stood behind this chunk, [4] the chunk's own result (cmx_vote_last), then the shadows' two sticky hand-off flags
-  float* d_mix0 = nullptr;                             // where instance 0 wrote this chunk's mixer outputs (d_shmix[0] or the debug area)
-  hipEvent_t ev_sh[2] = {nullptr, nullptr}, ev_vote = nullptr;
-  bool voted = false;                                  // this slot's chunk has a vote behind it: whoever waits for ev_mix1 also waits for ev_vote
-  // shadow context stages (cmx_pipeline_set_ctx_shadow): allocated at the first begin, nothing of it otherwise
-  float* d_cxp[2] = {nullptr, nullptr};                // [8 max][64] model outputs of shadow i + 1 (compact form)
-  uint32_t* d_cxsel[2] = {nullptr, nullptr};           // [8 max][47] its selectors
-  unsigned long long* h_cxvote = nullptr;              // pinned [12]: the context vote's record as it stood behind this chunk, then the chunk's own result
-  hipEvent_t ev_cx[2] = {nullptr, nullptr}, ev_cxvote = nullptr;
-  bool cxvoted = false;                                // this slot's chunk has a context vote behind it: slot_done waits for ev_cxvote too
-  // shadow LSTM stages (cmx_pipeline_set_lstm_shadow): allocated at the first begin, nothing of it otherwise
-  float* d_lsout[2] = {nullptr, nullptr};              // [max][256] distributions of shadow i + 1
-  float* d_lsp[2] = {nullptr, nullptr};                // [8 max] its bit predictions (dense)
-  int* d_lsex[2] = {nullptr, nullptr};                 // [8 max] its ex
-  unsigned long long* h_lsvote = nullptr;              // pinned [12]: the LSTM vote's record as it stood behind this chunk, then the chunk's own result; then the shadows' two sticky hand-off flags
-  hipEvent_t ev_ls[2] = {nullptr, nullptr}, ev_lsvote = nullptr;
-  bool lsvoted = false;                                // this slot's chunk has an LSTM vote behind it: slot_done waits for ev_lsvote too
-  // shadow fxcm stages (cmx_pipeline_set_fxcm_shadow): allocated at the first begin (or pretrain), nothing of it otherwise
-  float* d_fsp[2] = {nullptr, nullptr};                // [8 max][434] rows of shadow i + 1 (columns 3..433 used)
-  unsigned long long* h_fsvote = nullptr;              // pinned [12]: the fxcm vote's record as it stood behind this chunk, then the chunk's own result; then the shadows' two sticky hand-off flags
-  hipEvent_t ev_fs[2] = {nullptr, nullptr}, ev_fsvote = nullptr;
-  bool fsvoted = false;                                // this slot's chunk has an fxcm vote behind it: slot_done waits for ev_fsvote too (the vote reads the slot's layer-0 rows in place)
+  // shadow stages (pipeline_shadow.h): allocated at a kind's first chunk (or pretrain), nothing of it otherwise
+  ShadowSlot sh[SH_KINDS];
+  float* d_mix0 = nullptr;                             // mixing network's repair: where instance 0 wrote this chunk's mixer outputs (sh[SH_MIX].d_own or the debug area)
   // stream journal (cmx_pipeline_set_journal): allocated at the set call, nothing of it otherwise
   unsigned long long* d_jr = nullptr;                  // the chunk's partial records on the device
   uint64_t* h_jr = nullptr;                            // pinned: their copy, complete when ev_jr is
@@ -241,33 +221,13 @@ struct cmx_pipeline {
   int last_slot = -1;
   double tot_ms[3] = {0, 0, 0};  // HIP-event time of every finished chunk's stages since the last reset
   uint64_t tot_chunks = 0;
-  int shadow = 0;                // cmx_pipeline_set_shadow: shadow mixing networks beside h->mix (0 = off: nothing below exists)
-  hipStream_t s_sh[2] = {nullptr, nullptr};   // their streams (from the factory, at set_shadow: the queue budget refuses there)
-  cmx_mixnet_t* sh[2] = {nullptr, nullptr};   // created at the first finish
-  cmx_vote_t* vote = nullptr;
-  uint64_t vote_bits = 0;        // stream bits handed to the vote so far
+  ShadowSet sh[SH_KINDS];        // cmx_pipeline_set_shadow and its three kin: shadow stages beside h->mix, h->ctx, h->lstm, h->fxcm (pipeline_shadow.h)
   // repair on the majority (cmx_pipeline_set_shadow_repair; 0 = off: wait / sync are the code without it)
   int repair_max = 0;
   uint64_t repairs = 0;          // repairs made
   uint64_t repaired_events = 0;  // chunks with a non-agreeing vote that those repairs covered (the vote's sticky record goes on counting them: [3])
   uint64_t repaired_upto = 0;    // chunks below this index had left the instances when the last repair was made
   uint64_t repair_log[CMX_REPAIR_LOG][CMX_REPAIR_WORDS] = {};   // ring of the last repairs, entry number r at [r % CMX_REPAIR_LOG]
-  int ctx_shadow = 0;            // cmx_pipeline_set_ctx_shadow: shadow context stages beside h->ctx (0 = off: nothing below exists)
-  hipStream_t s_cx[2] = {nullptr, nullptr};       // their streams (from the factory, at set_ctx_shadow: the queue budget refuses there)
-  cmx_ctxmodels_t* cx[2] = {nullptr, nullptr};    // compact handles, created at the first begin (or pretrain)
-  cmx_ctxvote_t* cxvote = nullptr;
-  uint64_t cxvote_bits = 0;      // stream bits handed to the context vote so far
-  int lstm_shadow = 0;           // cmx_pipeline_set_lstm_shadow: shadow LSTM stages beside h->lstm (0 = off: nothing below exists)
-  hipStream_t s_ls[2] = {nullptr, nullptr};       // their streams (from the factory, at set_lstm_shadow: the queue budget refuses there)
-  cmx_lstm_t* ls[2] = {nullptr, nullptr};         // created at the first begin
-  cmx_lstmvote_t* lsvote = nullptr;
-  uint64_t lsvote_bytes = 0;     // stream bytes handed to the LSTM vote so far
-  int fxcm_shadow = 0;           // cmx_pipeline_set_fxcm_shadow: shadow fxcm stages beside h->fxcm (0 = off: nothing below exists)
-  hipStream_t s_fs[2] = {nullptr, nullptr};       // their streams (from the factory, at set_fxcm_shadow: the queue budget refuses there)
-  cmx_fxcm_t* fs[2] = {nullptr, nullptr};         // shadow handles without a parser, created at the first begin or at pretrain
-  float* d_fs_scratch[2] = {nullptr, nullptr};    // pretraining writes each shadow's (discarded) rows here
-  cmx_fxcmvote_t* fsvote = nullptr;
-  uint64_t fsvote_bits = 0;      // stream bits handed to the fxcm vote so far
   bool pretrained = false;       // cmx_pipeline_pretrain has run: shadow context stages set after it would start untrained
   float* dbg_mix = nullptr;      // diagnosis (cmx_pipeline_debug_mix_out): the 47 mixer outputs of every bit, [bit][47], as far as dbg_mix_cap bits
   uint64_t dbg_mix_cap = 0, dbg_mix_bits = 0;
@@ -280,6 +240,56 @@ struct cmx_pipeline {
 };
 
 namespace {
+// ---- the four kinds of shadow stages (pipeline_shadow.h), in ShadowId's order ----
+// Per entry: id, wgs, stream_flag, probe_cap, strict, needs_fxcm, pretrained, pretrained_first, diff_idle, rec_words, alloc_fail; then the callbacks own,
+// create, destroy, fail_flag, check, state_diff, vote_create, vote_destroy, report, record, sizes.
+const ShadowKind kShadow[SH_KINDS] = {
+    // the mixing network's: built at the first finish (~2.8 GB each); slot buffers p [8 max] and mixer outputs [8 max][47], the latter for instance 0 too
+    {SH_MIX, 27, 1, 24, true, false, nullptr, false, false, 14, "cmx_pipeline_finish: buffer allocation for the shadow mixing networks failed",
+     [](cmx_pipeline* h) -> void* { return h->mix; },
+     [](cmx_pipeline* h) -> void* {
+       cmx_mixnet_t* m = cmx_mixnet_create(h->device);
+       if (m && cmx_mixnet_set_upload_stream(m, h->s_up)) { cmx_mixnet_destroy(m); m = nullptr; }
+       return m;
+     },
+     [](void* x) { cmx_mixnet_destroy((cmx_mixnet_t*)x); }, [](void* x) -> const void* { return cmx_mixnet_error_flag((cmx_mixnet_t*)x); },
+     [](void* x) { return cmx_mixnet_sync((cmx_mixnet_t*)x) ? 1 : 0; }, [](void* a, void* b, uint64_t* out) { return cmx_mixnet_state_diff((cmx_mixnet_t*)a, (cmx_mixnet_t*)b, out); },
+     [](int device, int n) -> void* { return cmx_vote_create(device, n); }, [](void* v) { cmx_vote_destroy((cmx_vote_t*)v); }, [](void* v, uint64_t* out) { return cmx_vote_report((cmx_vote_t*)v, out); },
+     [](void* v) { return cmx_vote_record((cmx_vote_t*)v); },
+     [](size_t n, size_t b[3], size_t* own) { b[0] = 8 * n * 4; b[1] = *own = 8 * n * CMX_N_MIXERS * 4; }},
+    // the context stage's: compact handles, built at the first begin or at pretrain (which trains every instance); model outputs [8 max][64] and selectors [8 max][47]
+    {SH_CTX, 1, 0, 24, false, false, "a shadow that missed the dictionary disagrees in the first chunk", false, false, 12, "cmx_pipeline_begin: buffer allocation for the shadow context stages failed",
+     [](cmx_pipeline* h) -> void* { return h->ctx; }, [](cmx_pipeline* h) -> void* { return cmx_ctxmodels_create_compact(h->vocab, h->device); },
+     [](void* x) { cmx_ctxmodels_destroy((cmx_ctxmodels_t*)x); }, nullptr, [](void* x) { return cmx_ctxmodels_sync((cmx_ctxmodels_t*)x) ? 1 : 0; },
+     [](void* a, void* b, uint64_t* out) { return cmx_ctxmodels_state_diff((cmx_ctxmodels_t*)a, (cmx_ctxmodels_t*)b, out); },
+     [](int device, int n) -> void* { return cmx_ctxvote_create(device, n); }, [](void* v) { cmx_ctxvote_destroy((cmx_ctxvote_t*)v); }, [](void* v, uint64_t* out) { return cmx_ctxvote_report((cmx_ctxvote_t*)v, out); },
+     [](void* v) { return cmx_ctxvote_record((cmx_ctxvote_t*)v); },
+     [](size_t n, size_t b[3], size_t*) { b[0] = 8 * n * CMX_CTX_COMPACT_STRIDE * 4; b[1] = 8 * n * CMX_N_MIXERS * 4; }},
+    // the LSTM's: as the stream's own (cmx_pipeline_create), built at the first begin; allowed after pretrain: the LSTM is not pretrained.
+    // Distributions [max][256], bit predictions [8 max] (dense), ex [8 max]
+    {SH_LSTM, 52, 0, 26, true, false, nullptr, false, false, 14, "cmx_pipeline_begin: buffer allocation for the shadow LSTM stages failed",
+     [](cmx_pipeline* h) -> void* { return h->lstm; }, [](cmx_pipeline* h) -> void* { return cmx_lstm_create(h->vocab, 31, h->device); },
+     [](void* x) { cmx_lstm_destroy((cmx_lstm_t*)x); }, [](void* x) -> const void* { return cmx_lstm_fail_flag((cmx_lstm_t*)x); }, [](void* x) { return cmx_lstm_failed((cmx_lstm_t*)x) ? 2 : 0; },
+     [](void* a, void* b, uint64_t* out) { return cmx_lstm_state_diff((cmx_lstm_t*)a, (cmx_lstm_t*)b, out); },
+     [](int device, int n) -> void* { return cmx_lstmvote_create(device, n); }, [](void* v) { cmx_lstmvote_destroy((cmx_lstmvote_t*)v); }, [](void* v, uint64_t* out) { return cmx_lstmvote_report((cmx_lstmvote_t*)v, out); },
+     [](void* v) { return cmx_lstmvote_record((cmx_lstmvote_t*)v); },
+     [](size_t n, size_t b[3], size_t*) { b[0] = n * 256 * 4; b[1] = b[2] = 8 * n * 4; }},
+    // fxcm's: handles without a parser (4.4 GB each), built at the first begin or at pretrain; refused after pretrain: fxcm IS pretrained (predictor.cpp:471-476).
+    // Rows [8 max][434] (columns 3..433 used); the vote reads instance 0's rows in the slot's layer-0 rows in place
+    {SH_FXCM, 4, 0, 28, false, true, "fxcm learns the dictionary: a shadow made now would have missed it", true, true, 14, "cmx_pipeline_begin: buffer allocation for the shadow fxcm stages failed",
+     [](cmx_pipeline* h) -> void* { return h->fxcm; }, [](cmx_pipeline* h) -> void* { return cmx_fxcm_create_shadow(h->device); },
+     [](void* x) { cmx_fxcm_destroy((cmx_fxcm_t*)x); }, [](void* x) -> const void* { return cmx_fxcm_fail_flag((cmx_fxcm_t*)x); }, [](void* x) { return cmx_fxcm_failed((cmx_fxcm_t*)x) ? 2 : 0; },
+     [](void* a, void* b, uint64_t* out) { return cmx_fxcm_state_diff((cmx_fxcm_t*)a, (cmx_fxcm_t*)b, out); },
+     [](int device, int n) -> void* { return cmx_fxcmvote_create(device, n); }, [](void* v) { cmx_fxcmvote_destroy((cmx_fxcmvote_t*)v); }, [](void* v, uint64_t* out) { return cmx_fxcmvote_report((cmx_fxcmvote_t*)v, out); },
+     [](void* v) { return cmx_fxcmvote_record((cmx_fxcmvote_t*)v); },
+     [](size_t n, size_t b[3], size_t*) { b[0] = 8 * n * 434 * sizeof(float); }},
+};
+// where the kinds are gone through behind the stages themselves: a decoder's drop, slot_done, cmx_pipeline_sync
+const ShadowId kShadowLast[SH_KINDS] = {SH_CTX, SH_LSTM, SH_FXCM, SH_MIX};
+
+// begin / finish: a failure behind its construction leaves a chunk's stages half-enqueued, and the handle void
+struct ChunkTxn { cmx_pipeline* h; bool ok = false; ~ChunkTxn() { if (!ok) h->failed = true; } };
+
 void collect(cmx_pipeline* h, Slot& s) {  // the slot's chunk has finished (its ev_mix1 was waited for)
   if (!s.untimed) return;
   float ms[3] = {0, 0, 0};
@@ -300,10 +310,8 @@ static int probe_streams(cmx_pipeline* h) {
   hipStream_t q[28] = {h->s_lstm, h->s_ctx, h->s_mix, h->s_up, h->s_fx, h->s_p8, h->late ? h->late->s_bm : nullptr};
   int n = 7;
   if (h->p8) n += cmx_p8stage_streams(h->p8, q + n, 24 - n);
-  for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_sh[i];   // (null entries are skipped)
-  for (int i = 0; i < 2 && n < 24; ++i) q[n++] = h->s_cx[i];
-  for (int i = 0; i < 2 && n < 26; ++i) q[n++] = h->s_ls[i];
-  for (int i = 0; i < 2 && n < 28; ++i) q[n++] = h->s_fs[i];
+  for (const ShadowKind& K : kShadow)
+    for (int i = 0; i < 2 && n < K.probe_cap; ++i) q[n++] = h->sh[K.id].q[i];   // (null entries are skipped)
   const int all = cmx_overlap_probe(q, n, &h->probe_n);
   h->probe_all = all < 0 ? 0 : all;
   h->overlap = all < 0 ? -1 : all == h->probe_n ? 1 : 0;
@@ -314,10 +322,9 @@ static int probe_streams(cmx_pipeline* h) {
 static hipError_t slot_done(Slot& s) {
   hipError_t e = hipEventSynchronize(s.ev_mix1);
   if (e == hipSuccess && s.journalled) e = hipEventSynchronize(s.ev_jr);
-  if (e == hipSuccess && s.cxvoted) e = hipEventSynchronize(s.ev_cxvote);
-  if (e == hipSuccess && s.lsvoted) e = hipEventSynchronize(s.ev_lsvote);
-  if (e == hipSuccess && s.fsvoted) e = hipEventSynchronize(s.ev_fsvote);
-  return e == hipSuccess && s.voted ? hipEventSynchronize(s.ev_vote) : e;
+  for (ShadowId k : kShadowLast)
+    if (e == hipSuccess && s.sh[k].voted) e = hipEventSynchronize(s.sh[k].ev_vote);
+  return e;
 }
 // the journal's partial records of every finished chunk below `upto`, in stream order (each chunk's copy is waited for: they land in order on s_mix)
 static int journal_fold(cmx_pipeline* h, uint64_t upto) {
@@ -340,52 +347,6 @@ static void journal_drop(cmx_pipeline* h) {
   }
   cmx_journal_destroy(h->jr);
   h->jr = nullptr; h->jr_cap = 0;
-}
-// What a context vote's record (cmx_ctxvote_report's eight words) says, for an error message
-static std::string ctx_vote_text(const unsigned long long r[8]) {
-  static const int kFirstCol = 2025 - 3;   // lane order: layer-0 columns 0, 1, 2, 2025..2075
-  std::string s = "context shadow vote: the " + std::to_string(r[2]) + " context-stage instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream bit " +
-                  std::to_string(r[4]) + ", " + (r[5] < 54 ? "layer-0 column " + std::to_string(r[5] < 3 ? r[5] : kFirstCol + r[5]) : "selector " + std::to_string(r[5] - 54)) + ": ";
-  if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
-  else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own stage)" : "");
-  return s + " (the stream's output is void)";
-}
-// What an LSTM vote's record (cmx_lstmvote_report's eight words) says, for an error message
-static std::string lstm_vote_text(const unsigned long long r[8]) {
-  const unsigned long long c = r[5];
-  std::string s = "LSTM shadow vote: the " + std::to_string(r[2]) + " LSTM-stage instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream byte " +
-                  std::to_string(r[4]) + ", " + (c < 256 ? "distribution entry " + std::to_string(c) : c < 264 ? "bit " + std::to_string(c - 256) + "'s prediction (layer-0 column 2077)" :
-                                                 "bit " + std::to_string(c - 264) + "'s ex") + ": ";
-  if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
-  else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own stage)" : "");
-  return s + " (the stream's output is void)";
-}
-// What an fxcm vote's record (cmx_fxcmvote_report's eight words) says, for an error message
-static std::string fxcm_vote_text(const unsigned long long r[8]) {
-  std::string s = "fxcm shadow vote: the " + std::to_string(r[2]) + " fxcm-stage instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream bit " +
-                  std::to_string(r[4]) + " (byte " + std::to_string(r[4] >> 3) + ", bit " + std::to_string(r[4] & 7) + "), fxcm column " + std::to_string(r[5]) + " (layer-0 column " +
-                  std::to_string(3 + r[5]) + "): ";
-  if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
-  else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own stage)" : "");
-  return s + " (the stream's output is void)";
-}
-// What a vote record (cmx_vote_report's eight words) says, for an error message
-static std::string vote_text(const unsigned long long r[8]) {
-  std::string s = "shadow vote: the " + std::to_string(r[2]) + " mixing-network instances disagree in " + std::to_string(r[7]) + " value(s) of the chunk, first at stream bit " +
-                  std::to_string(r[4]) + ", " + (r[5] < 47 ? "mixer " + std::to_string(r[5]) : std::string("final p")) + ": ";
-  if (r[6] == ~0ull) s += "no majority between " + std::to_string(r[2]) + " instances";
-  else s += "instance " + std::to_string(r[6]) + " is the odd one" + (r[6] == 0 ? " (the stream's own network)" : "");
-  return s + " (the stream's output is void)";
-}
-static std::string origin_text(uint64_t m0, uint64_t m12) {
-  for (int i = 0; i < 26; ++i) if (m0 >> i & 1) return "mixer " + std::to_string(i);
-  for (int i = 0; i < 21; ++i) if (m12 >> i & 1) return "mixer " + std::to_string(26 + i);
-  return "no mixer row (tables / scalars only)";
-}
-// one entry of the repair log (cmx_pipeline_shadow_repairs) in words
-static std::string repair_entry_text(const uint64_t* e) {
-  return "chunk " + std::to_string(e[0]) + ", stream bit " + std::to_string(e[1]) + ", " + (e[2] < 47 ? "mixer " + std::to_string(e[2]) : std::string("final p")) + ", instance " +
-         std::to_string(e[3]) + " odd, " + std::to_string(e[5]) + " state word(s) repaired, origin " + origin_text(e[12], e[13]);
 }
 // the repairs made so far, for the message of a stop behind them
 static std::string repairs_text(const cmx_pipeline* h) {
@@ -436,98 +397,29 @@ static void wg_unclaim(cmx_pipeline* h, int n) {
   g_wg_used[h->device & 63] -= n;
   h->wgs -= n;
 }
-// everything cmx_pipeline_set_shadow and the first finish behind it made: the device is idle
-static void shadow_drop(cmx_pipeline* h) {
-  if (!h->shadow) return;
+// everything the set call of one kind and the first chunk (or pretrain) behind it made: the device is idle. fxcm's go before the stream's own fxcm handle does
+static void shadow_drop(cmx_pipeline* h, const ShadowKind& K) {
+  ShadowSet& S = h->sh[K.id];
+  if (!S.k) return;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  cmx_vote_destroy(h->vote); h->vote = nullptr;
+  K.vote_destroy(S.vote); S.vote = nullptr;
   for (int i = 0; i < 2; ++i) {
-    cmx_mixnet_destroy(h->sh[i]); h->sh[i] = nullptr;
-    if (h->s_sh[i]) cmx_destroy_stream(h->s_sh[i]);
-    h->s_sh[i] = nullptr;
+    if (S.inst[i]) K.destroy(S.inst[i]);
+    if (S.q[i]) cmx_destroy_stream(S.q[i]);
+    if (S.d_scratch[i]) (void)hipFree(S.d_scratch[i]);
+    S.inst[i] = nullptr; S.q[i] = nullptr; S.d_scratch[i] = nullptr;
   }
   for (Slot& s : h->slot) {
-    for (float*& p : s.d_shp) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float*& p : s.d_shmix) { if (p) (void)hipFree(p); p = nullptr; }
-    if (s.h_vote) (void)hipHostFree(s.h_vote);
-    s.h_vote = nullptr;
-    for (hipEvent_t* e : {&s.ev_sh[0], &s.ev_sh[1], &s.ev_vote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    s.voted = false;
+    ShadowSlot& w = s.sh[K.id];
+    for (void** p : {&w.d[0][0], &w.d[0][1], &w.d[0][2], &w.d[1][0], &w.d[1][1], &w.d[1][2], &w.d_own}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    if (w.rec) (void)hipHostFree(w.rec);
+    w.rec = nullptr;
+    for (hipEvent_t* e : {&w.ev[0], &w.ev[1], &w.ev_vote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    w.voted = false;
   }
-  wg_unclaim(h, 27 * h->shadow);
-  h->shadow = 0;
-}
-
-// everything cmx_pipeline_set_ctx_shadow and the first begin (or pretrain) behind it made
-static void ctx_shadow_drop(cmx_pipeline* h) {
-  if (!h->ctx_shadow) return;
-  (void)hipSetDevice(h->device);
-  (void)hipDeviceSynchronize();
-  cmx_ctxvote_destroy(h->cxvote); h->cxvote = nullptr;
-  for (int i = 0; i < 2; ++i) {
-    cmx_ctxmodels_destroy(h->cx[i]); h->cx[i] = nullptr;
-    if (h->s_cx[i]) cmx_destroy_stream(h->s_cx[i]);
-    h->s_cx[i] = nullptr;
-  }
-  for (Slot& s : h->slot) {
-    for (float*& p : s.d_cxp) { if (p) (void)hipFree(p); p = nullptr; }
-    for (uint32_t*& p : s.d_cxsel) { if (p) (void)hipFree(p); p = nullptr; }
-    if (s.h_cxvote) (void)hipHostFree(s.h_cxvote);
-    s.h_cxvote = nullptr;
-    for (hipEvent_t* e : {&s.ev_cx[0], &s.ev_cx[1], &s.ev_cxvote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    s.cxvoted = false;
-  }
-  wg_unclaim(h, h->ctx_shadow);
-  h->ctx_shadow = 0;
-}
-
-// everything cmx_pipeline_set_lstm_shadow and the first begin behind it made
-static void lstm_shadow_drop(cmx_pipeline* h) {
-  if (!h->lstm_shadow) return;
-  (void)hipSetDevice(h->device);
-  (void)hipDeviceSynchronize();
-  cmx_lstmvote_destroy(h->lsvote); h->lsvote = nullptr;
-  for (int i = 0; i < 2; ++i) {
-    cmx_lstm_destroy(h->ls[i]); h->ls[i] = nullptr;
-    if (h->s_ls[i]) cmx_destroy_stream(h->s_ls[i]);
-    h->s_ls[i] = nullptr;
-  }
-  for (Slot& s : h->slot) {
-    for (float*& p : s.d_lsout) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float*& p : s.d_lsp) { if (p) (void)hipFree(p); p = nullptr; }
-    for (int*& p : s.d_lsex) { if (p) (void)hipFree(p); p = nullptr; }
-    if (s.h_lsvote) (void)hipHostFree(s.h_lsvote);
-    s.h_lsvote = nullptr;
-    for (hipEvent_t* e : {&s.ev_ls[0], &s.ev_ls[1], &s.ev_lsvote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    s.lsvoted = false;
-  }
-  wg_unclaim(h, 52 * h->lstm_shadow);
-  h->lstm_shadow = 0;
-}
-
-// everything cmx_pipeline_set_fxcm_shadow and the first begin (or pretrain) behind it made; before the stream's own fxcm handle goes
-static void fxcm_shadow_drop(cmx_pipeline* h) {
-  if (!h->fxcm_shadow) return;
-  (void)hipSetDevice(h->device);
-  (void)hipDeviceSynchronize();
-  cmx_fxcmvote_destroy(h->fsvote); h->fsvote = nullptr;
-  for (int i = 0; i < 2; ++i) {
-    cmx_fxcm_destroy(h->fs[i]); h->fs[i] = nullptr;
-    if (h->s_fs[i]) cmx_destroy_stream(h->s_fs[i]);
-    h->s_fs[i] = nullptr;
-    if (h->d_fs_scratch[i]) (void)hipFree(h->d_fs_scratch[i]);
-    h->d_fs_scratch[i] = nullptr;
-  }
-  for (Slot& s : h->slot) {
-    for (float*& p : s.d_fsp) { if (p) (void)hipFree(p); p = nullptr; }
-    if (s.h_fsvote) (void)hipHostFree(s.h_fsvote);
-    s.h_fsvote = nullptr;
-    for (hipEvent_t* e : {&s.ev_fs[0], &s.ev_fs[1], &s.ev_fsvote}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    s.fsvoted = false;
-  }
-  wg_unclaim(h, 4 * h->fxcm_shadow);
-  h->fxcm_shadow = 0;
+  wg_unclaim(h, K.wgs * S.k);
+  S.k = 0;
 }
 
 void cmx_pipeline_destroy(cmx_pipeline_t* h) {
@@ -548,10 +440,7 @@ void cmx_pipeline_destroy(cmx_pipeline_t* h) {
     delete h->late;
     h->late = nullptr;
   }
-  shadow_drop(h);
-  ctx_shadow_drop(h);
-  lstm_shadow_drop(h);
-  fxcm_shadow_drop(h);
+  for (const ShadowKind& K : kShadow) shadow_drop(h, K);   // (fxcm's shadows before h->fxcm below: they run on its records)
   wg_release(h);
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
@@ -725,8 +614,8 @@ int cmx_pipeline_enable_paq8(cmx_pipeline_t* h) {
 int cmx_pipeline_set_tolerance(cmx_pipeline_t* h, int on) {
   if (!h) { cmx_set_err("cmx_pipeline_set_tolerance: null handle"); return 1; }
   if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_tolerance: only before the first chunk"); return 1; }
-  if (on && h->shadow) { cmx_set_err("cmx_pipeline_set_tolerance: shadow mixing networks are set (the vote compares strict kernels)"); return 1; }
-  if (on && h->lstm_shadow) { cmx_set_err("cmx_pipeline_set_tolerance: shadow LSTM stages are set (the vote compares strict kernels)"); return 1; }
+  for (const ShadowKind& K : kShadow)
+    if (on && K.strict && h->sh[K.id].k) { cmx_set_err(std::string("cmx_pipeline_set_tolerance: ") + shadow_words(K.id).noun + "s are set (the vote compares strict kernels)"); return 1; }
   // the mixing network first (it can refuse: after the stream's first bit); the LSTM's switch (its weight-update contraction
   // on the matrix cores) follows and is rolled back with the network's if it fails, so that the two never disagree about the mode
   const int was = cmx_mixnet_mode(h->mix);
@@ -746,274 +635,170 @@ int cmx_pipeline_verify_report(cmx_pipeline_t* h, uint64_t out[8]) {
   if (!h) { cmx_set_err("cmx_pipeline_verify_report: null handle"); return 1; }
   return cmx_mixnet_verify_report(h->mix, out);
 }
-// ---- shadow mixing networks and their vote (include/cmix_amd.h; mixnet_vote.hip) ----
-// Reserves here what can be refused -- k streams of the factory (the queue budget) and 27 resident workgroups per shadow --; the k handles
-// (~2.8 GB each) and the per-slot buffers are made at the first finish.
-int cmx_pipeline_set_shadow(cmx_pipeline_t* h, int k) {
-  if (!h) { cmx_set_err("cmx_pipeline_set_shadow: null handle"); return 1; }
-  if (k < 0 || k > 2) { cmx_set_err("cmx_pipeline_set_shadow: k must be 0, 1 or 2 shadow mixing networks (a vote has 2 or 3 instances)"); return 1; }
-  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_shadow: only before the first chunk"); return 1; }
-  if (k && (h->lstm_tolerance || cmx_mixnet_mode(h->mix) == 1)) { cmx_set_err("cmx_pipeline_set_shadow: the tolerance switch is set (the vote compares strict kernels)"); return 1; }
+// ---- shadow stages and their votes (include/cmix_amd.h; pipeline_shadow.h; mixnet_vote.hip, ctxmodels_vote.hip, lstm_vote.hip, fxcm_vote.hip) ----
+// A set call reserves what can be refused -- k streams of the factory (the queue budget) and the kind's resident workgroups per shadow --; the k handles, the
+// vote and the per-slot buffers are made at the kind's first chunk or at pretrain (shadow_build).
+static int shadow_set(cmx_pipeline* h, const ShadowKind& K, int k) {
+  const std::string fn = shadow_fn(K.id, "cmx_pipeline_set_", "");
+  if (!h) { cmx_set_err(fn + ": null handle"); return 1; }
+  if (k < 0 || k > 2) { cmx_set_err(fn + ": k must be 0, 1 or 2 " + shadow_words(K.id).noun + "s (a vote has 2 or 3 instances)"); return 1; }
+  if (h->chunks || h->late) { cmx_set_err(fn + ": only before the first chunk"); return 1; }
+  if (K.strict && k && (h->lstm_tolerance || cmx_mixnet_mode(h->mix) == 1)) { cmx_set_err(fn + ": the tolerance switch is set (the vote compares strict kernels)"); return 1; }
+  if (K.needs_fxcm && k && !h->fxcm) { cmx_set_err(fn + ": the fxcm stage is not on the device (cmx_pipeline_enable_fxcm first)"); return 1; }
+  ShadowSet& S = h->sh[K.id];
+  auto pretrained = [&]() {   // a shadow made now would have missed the dictionary
+    if (!K.pretrained || !k || !h->pretrained || k == S.k) return false;
+    cmx_set_err(fn + ": only before cmx_pipeline_pretrain (" + K.pretrained + ")");
+    return true;
+  };
+  if (K.pretrained_first && pretrained()) return 1;
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
-  if (k == h->shadow) return 0;
-  shadow_drop(h);
+  if (k == S.k) return 0;
+  if (pretrained()) return 1;
+  shadow_drop(h, K);
   if (k == 0) return probe_streams(h) < 0 ? 1 : 0;
-  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) {
-    cmx_set_err("cmx_pipeline_set_shadow: this process holds " + std::to_string(cmx_hw_queues(h->device)) + " dedicated hardware queues on device " + std::to_string(h->device) +
-                " and " + std::to_string(k) + " shadow mixing network(s) need one each, the limit is " + std::to_string(CMX_MAX_HW_QUEUES));
-    return 1;
-  }
-  if (!wg_claim(h, 27 * k, "cmx_pipeline_set_shadow")) return 1;
-  h->shadow = k;
+  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) { cmx_set_err(shadow_queue_text(K.id, cmx_hw_queues(h->device), h->device, k, CMX_MAX_HW_QUEUES)); return 1; }
+  if (!wg_claim(h, K.wgs * k, fn.c_str())) return 1;
+  S.k = k;
   for (int i = 0; i < k; ++i)
-    if (cmx_make_stream(&h->s_sh[i], 1)) { shadow_drop(h); return 1; }   // (the factory has said why)
+    if (cmx_make_stream(&S.q[i], K.stream_flag)) { shadow_drop(h, K); return 1; }   // (the factory has said why)
   return probe_streams(h) < 0 ? 1 : 0;
 }
-// the first finish with shadows: the handles, the vote, the per-slot buffers
-static int shadow_build(cmx_pipeline* h) {
-  const size_t T = 8 * h->max_chunk;
-  h->vote = cmx_vote_create(h->device, 1 + h->shadow);
-  if (!h->vote) return 1;
-  for (int i = 0; i < h->shadow; ++i) {
-    h->sh[i] = cmx_mixnet_create(h->device);
-    if (!h->sh[i] || cmx_mixnet_set_upload_stream(h->sh[i], h->s_up)) return 1;
-  }
+// a kind's first chunk (or pretrain) with shadows: the vote, the handles, the per-slot buffers
+static int shadow_build(cmx_pipeline* h, const ShadowKind& K) {
+  ShadowSet& S = h->sh[K.id];
+  S.vote = K.vote_create(h->device, 1 + S.k);
+  if (!S.vote) return 1;
+  for (int i = 0; i < S.k; ++i)
+    if (!(S.inst[i] = K.create(h))) return 1;
+  size_t bytes[3] = {0, 0, 0}, own = 0;
+  K.sizes(h->max_chunk, bytes, &own);
   bool ok = hipSetDevice(h->device) == hipSuccess;
   for (Slot& s : h->slot) {
-    for (int i = 0; i < h->shadow; ++i) ok = ok && hipMalloc((void**)&s.d_shp[i], T * 4) == hipSuccess && hipEventCreateWithFlags(&s.ev_sh[i], hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i <= h->shadow; ++i) ok = ok && hipMalloc((void**)&s.d_shmix[i], T * CMX_N_MIXERS * 4) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_vote, 14 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_vote, hipEventDisableTiming) == hipSuccess;
-    if (ok) memset(s.h_vote, 0, 14 * 8);
+    ShadowSlot& w = s.sh[K.id];
+    for (int i = 0; i < S.k; ++i) {
+      for (int j = 0; j < 3; ++j)
+        if (bytes[j]) ok = ok && hipMalloc(&w.d[i][j], bytes[j]) == hipSuccess;
+      ok = ok && hipEventCreateWithFlags(&w.ev[i], hipEventDisableTiming) == hipSuccess;
+    }
+    if (own) ok = ok && hipMalloc(&w.d_own, own) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&w.rec, K.rec_words * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&w.ev_vote, hipEventDisableTiming) == hipSuccess;
+    if (ok) memset(w.rec, 0, K.rec_words * 8);
   }
-  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_finish: buffer allocation for the shadow mixing networks failed"); return 1; }
+  if (!ok) { (void)hipGetLastError(); cmx_set_err(K.alloc_fail); return 1; }
   return 0;
 }
-int cmx_pipeline_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) {
-  if (!h || !out) { cmx_set_err("cmx_pipeline_shadow_report: bad argument"); return 1; }
-  if (!h->vote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
-  return cmx_vote_report(h->vote, out);
+// One chunk on every shadow of a kind, into the slot's buffers of its own, and the vote behind them: build at the first use; every shadow's stream waits for
+// `inputs` (null entries: not in use), runs (`run(i, stream)`: the kind's stage call) and leaves its sticky hand-off flag in the slot's record; the LAST
+// shadow's stream then waits for the stream's own stage (`stage_done`) and for the other shadow, and votes (`vote(stream, units so far)`: the kind's vote call)
+// over `units` bits (LSTM: bytes). Nothing downstream of the stream's own stage waits for any of this but slot_done.
+extern "C++" {   // (a template, inside the C ABI's block)
+template <class Run, class Vote>
+static int shadow_chunk(cmx_pipeline* h, const ShadowKind& K, Slot& s, std::initializer_list<hipEvent_t> inputs, hipEvent_t stage_done, size_t units, Run run, Vote vote) {
+  ShadowSet& S = h->sh[K.id];
+  ShadowSlot& w = s.sh[K.id];
+  if (!S.vote && shadow_build(h, K)) return 1;
+  for (int i = 0; i < S.k; ++i) {
+    hipStream_t q = S.q[i];
+    for (hipEvent_t e : inputs)
+      if (e) (void)hipStreamWaitEvent(q, e, 0);
+    if (run(i, q)) return 1;
+    if (K.fail_flag) (void)hipMemcpyAsync((unsigned*)(w.rec + 12) + i, K.fail_flag(S.inst[i]), 4, hipMemcpyDeviceToHost, q);
+    (void)hipEventRecord(w.ev[i], q);
+  }
+  hipStream_t q = S.q[S.k - 1];
+  (void)hipStreamWaitEvent(q, stage_done, 0);
+  for (int i = 0; i + 1 < S.k; ++i) (void)hipStreamWaitEvent(q, w.ev[i], 0);
+  if (vote(q, S.units)) return 1;
+  (void)hipMemcpyAsync(w.rec, K.record(S.vote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
+  (void)hipEventRecord(w.ev_vote, q);
+  w.voted = true;
+  S.units += units;
+  return 0;
 }
+}  // extern "C++"
+static int shadow_report(cmx_pipeline* h, ShadowId k, uint64_t out[8]) {
+  if (!h || !out) { cmx_set_err(shadow_fn(k, "cmx_pipeline_", "_report") + ": bad argument"); return 1; }
+  if (!h->sh[k].vote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
+  return kShadow[k].report(h->sh[k].vote, out);
+}
+// the guard of the four _values calls. 1: bad argument; 0 with *vote NULL: nothing voted yet, `words` are zero (the caller zeroes what else it returns)
+static int shadow_values_guard(cmx_pipeline* h, ShadowId k, uint32_t* words, size_t nwords, void** vote) {
+  if (!h || !words) { cmx_set_err(shadow_fn(k, "cmx_pipeline_", "_values") + ": bad argument"); return 1; }
+  *vote = h->sh[k].vote;
+  if (!*vote) memset(words, 0, nwords * 4);
+  return 0;
+}
+static void* shadow_instance(cmx_pipeline* h, ShadowId k, int i) { return i == 0 ? kShadow[k].own(h) : i > 0 && i <= h->sh[k].k ? h->sh[k].inst[i - 1] : nullptr; }
+static int shadow_state_diff(cmx_pipeline* h, ShadowId k, int a, int b, uint64_t* out) {
+  const std::string fn = shadow_fn(k, "cmx_pipeline_", "_state_diff");
+  if (!h || !out) { cmx_set_err(fn + ": bad argument"); return 1; }
+  void *x = shadow_instance(h, k, a), *y = shadow_instance(h, k, b);
+  if (!x || !y) { cmx_set_err(shadow_no_instance_text(k, fn)); return 1; }
+  if (kShadow[k].diff_idle && h->finished != h->chunks) { cmx_set_err(fn + ": between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
+  return kShadow[k].state_diff(x, y, out);
+}
+// the guard of the four debug_*_xor calls: the instance, or NULL (it has said why)
+static void* shadow_xor_instance(cmx_pipeline* h, ShadowId k, int instance) {
+  const std::string fn = shadow_fn(k, "cmx_pipeline_debug_", "_xor");
+  if (!h) { cmx_set_err(fn + ": null handle"); return nullptr; }
+  void* x = shadow_instance(h, k, instance);
+  if (!x) { cmx_set_err(shadow_no_instance_text(k, fn)); return nullptr; }
+  if (h->finished != h->chunks) { cmx_set_err(fn + ": between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return nullptr; }
+  return x;
+}
+int cmx_pipeline_set_shadow(cmx_pipeline_t* h, int k) { return shadow_set(h, kShadow[SH_MIX], k); }
+int cmx_pipeline_set_ctx_shadow(cmx_pipeline_t* h, int k) { return shadow_set(h, kShadow[SH_CTX], k); }
+int cmx_pipeline_set_lstm_shadow(cmx_pipeline_t* h, int k) { return shadow_set(h, kShadow[SH_LSTM], k); }
+int cmx_pipeline_set_fxcm_shadow(cmx_pipeline_t* h, int k) { return shadow_set(h, kShadow[SH_FXCM], k); }
+int cmx_pipeline_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) { return shadow_report(h, SH_MIX, out); }
+int cmx_pipeline_ctx_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) { return shadow_report(h, SH_CTX, out); }
+int cmx_pipeline_lstm_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) { return shadow_report(h, SH_LSTM, out); }
+int cmx_pipeline_fxcm_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) { return shadow_report(h, SH_FXCM, out); }
+int cmx_pipeline_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[20]) { return shadow_state_diff(h, SH_MIX, a, b, out); }
+int cmx_pipeline_ctx_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[16]) { return shadow_state_diff(h, SH_CTX, a, b, out); }
+int cmx_pipeline_lstm_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[16]) { return shadow_state_diff(h, SH_LSTM, a, b, out); }
+int cmx_pipeline_fxcm_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[CMX_FXCM_STATE_OUT]) { return shadow_state_diff(h, SH_FXCM, a, b, out); }
+// (the values and the xor calls differ in their arguments: one line each behind the shared guards)
 int cmx_pipeline_shadow_values(cmx_pipeline_t* h, uint32_t words[144], uint32_t sel[47], uint32_t* bit) {
-  if (!h || !words) { cmx_set_err("cmx_pipeline_shadow_values: bad argument"); return 1; }
-  if (!h->vote) { memset(words, 0, 144 * 4); if (sel) memset(sel, 0, 47 * 4); if (bit) *bit = 0; return 0; }
-  return cmx_vote_values(h->vote, words, sel, bit);
-}
-static cmx_mixnet_t* shadow_instance(cmx_pipeline* h, int i) { return i == 0 ? h->mix : i > 0 && i <= h->shadow ? h->sh[i - 1] : nullptr; }
-int cmx_pipeline_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[20]) {
-  if (!h || !out) { cmx_set_err("cmx_pipeline_shadow_state_diff: bad argument"); return 1; }
-  cmx_mixnet_t *x = shadow_instance(h, a), *y = shadow_instance(h, b);
-  if (!x || !y) { cmx_set_err("cmx_pipeline_shadow_state_diff: no such instance (0 = the stream's network, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
-  return cmx_mixnet_state_diff(x, y, out);
-}
-int cmx_pipeline_debug_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
-  if (!h) { cmx_set_err("cmx_pipeline_debug_shadow_xor: null handle"); return 1; }
-  cmx_mixnet_t* x = shadow_instance(h, instance);
-  if (!x) { cmx_set_err("cmx_pipeline_debug_shadow_xor: no such instance (0 = the stream's network, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
-  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
-  return cmx_mixnet_debug_state_xor(x, region, mixer, row, index, xor_mask);
-}
-// ---- shadow context stages and their vote (include/cmix_amd.h; ctxmodels_vote.hip) ----
-// Reserves here what can be refused -- k streams of the factory (the queue budget) and one resident workgroup per shadow --; the k compact handles,
-// the vote and the per-slot buffers are made at the first begin (or by pretrain, which trains every instance).
-int cmx_pipeline_set_ctx_shadow(cmx_pipeline_t* h, int k) {
-  if (!h) { cmx_set_err("cmx_pipeline_set_ctx_shadow: null handle"); return 1; }
-  if (k < 0 || k > 2) { cmx_set_err("cmx_pipeline_set_ctx_shadow: k must be 0, 1 or 2 shadow context stages (a vote has 2 or 3 instances)"); return 1; }
-  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_ctx_shadow: only before the first chunk"); return 1; }
-  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
-  if (k == h->ctx_shadow) return 0;
-  if (k && h->pretrained) { cmx_set_err("cmx_pipeline_set_ctx_shadow: only before cmx_pipeline_pretrain (a shadow that missed the dictionary disagrees in the first chunk)"); return 1; }
-  ctx_shadow_drop(h);
-  if (k == 0) return probe_streams(h) < 0 ? 1 : 0;
-  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) {
-    cmx_set_err("cmx_pipeline_set_ctx_shadow: this process holds " + std::to_string(cmx_hw_queues(h->device)) + " dedicated hardware queues on device " + std::to_string(h->device) +
-                " and " + std::to_string(k) + " shadow context stage(s) need one each, the limit is " + std::to_string(CMX_MAX_HW_QUEUES));
-    return 1;
-  }
-  if (!wg_claim(h, k, "cmx_pipeline_set_ctx_shadow")) return 1;
-  h->ctx_shadow = k;
-  for (int i = 0; i < k; ++i)
-    if (cmx_make_stream(&h->s_cx[i], 0)) { ctx_shadow_drop(h); return 1; }   // (the factory has said why)
-  return probe_streams(h) < 0 ? 1 : 0;
-}
-// the first begin (or pretrain) with shadow context stages: the handles, the vote, the per-slot buffers
-static int ctx_shadow_build(cmx_pipeline* h) {
-  const size_t T = 8 * h->max_chunk;
-  h->cxvote = cmx_ctxvote_create(h->device, 1 + h->ctx_shadow);
-  if (!h->cxvote) return 1;
-  for (int i = 0; i < h->ctx_shadow; ++i) {
-    h->cx[i] = cmx_ctxmodels_create_compact(h->vocab, h->device);
-    if (!h->cx[i]) return 1;
-  }
-  bool ok = hipSetDevice(h->device) == hipSuccess;
-  for (Slot& s : h->slot) {
-    for (int i = 0; i < h->ctx_shadow; ++i)
-      ok = ok && hipMalloc((void**)&s.d_cxp[i], T * CMX_CTX_COMPACT_STRIDE * 4) == hipSuccess && hipMalloc((void**)&s.d_cxsel[i], T * CMX_N_MIXERS * 4) == hipSuccess &&
-           hipEventCreateWithFlags(&s.ev_cx[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_cxvote, 12 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_cxvote, hipEventDisableTiming) == hipSuccess;
-    if (ok) memset(s.h_cxvote, 0, 12 * 8);
-  }
-  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_begin: buffer allocation for the shadow context stages failed"); return 1; }
-  return 0;
-}
-int cmx_pipeline_ctx_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) {
-  if (!h || !out) { cmx_set_err("cmx_pipeline_ctx_shadow_report: bad argument"); return 1; }
-  if (!h->cxvote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
-  return cmx_ctxvote_report(h->cxvote, out);
+  void* v;
+  if (shadow_values_guard(h, SH_MIX, words, 144, &v)) return 1;
+  if (!v) { if (sel) memset(sel, 0, 47 * 4); if (bit) *bit = 0; return 0; }
+  return cmx_vote_values((cmx_vote_t*)v, words, sel, bit);
 }
 int cmx_pipeline_ctx_shadow_values(cmx_pipeline_t* h, uint32_t words[3 * CMX_CTXVOTE_COLS], uint32_t* bit) {
-  if (!h || !words) { cmx_set_err("cmx_pipeline_ctx_shadow_values: bad argument"); return 1; }
-  if (!h->cxvote) { memset(words, 0, 3 * CMX_CTXVOTE_COLS * 4); if (bit) *bit = 0; return 0; }
-  return cmx_ctxvote_values(h->cxvote, words, bit);
-}
-static cmx_ctxmodels_t* ctx_shadow_instance(cmx_pipeline* h, int i) { return i == 0 ? h->ctx : i > 0 && i <= h->ctx_shadow ? h->cx[i - 1] : nullptr; }
-int cmx_pipeline_ctx_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[16]) {
-  if (!h || !out) { cmx_set_err("cmx_pipeline_ctx_shadow_state_diff: bad argument"); return 1; }
-  cmx_ctxmodels_t *x = ctx_shadow_instance(h, a), *y = ctx_shadow_instance(h, b);
-  if (!x || !y) { cmx_set_err("cmx_pipeline_ctx_shadow_state_diff: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
-  return cmx_ctxmodels_state_diff(x, y, out);
-}
-int cmx_pipeline_debug_ctx_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask) {
-  if (!h) { cmx_set_err("cmx_pipeline_debug_ctx_shadow_xor: null handle"); return 1; }
-  cmx_ctxmodels_t* x = ctx_shadow_instance(h, instance);
-  if (!x) { cmx_set_err("cmx_pipeline_debug_ctx_shadow_xor: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
-  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_ctx_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
-  return cmx_ctxmodels_debug_state_xor(x, region, lane, index, xor_mask);
-}
-// ---- shadow LSTM stages and their vote (include/cmix_amd.h; lstm_vote.hip) ----
-// Reserves here what can be refused -- k streams of the factory (the queue budget) and 52 resident workgroups per shadow --; the k handles, the vote
-// and the per-slot buffers are made at the first begin. Allowed after cmx_pipeline_pretrain: the LSTM is not pretrained.
-int cmx_pipeline_set_lstm_shadow(cmx_pipeline_t* h, int k) {
-  if (!h) { cmx_set_err("cmx_pipeline_set_lstm_shadow: null handle"); return 1; }
-  if (k < 0 || k > 2) { cmx_set_err("cmx_pipeline_set_lstm_shadow: k must be 0, 1 or 2 shadow LSTM stages (a vote has 2 or 3 instances)"); return 1; }
-  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_lstm_shadow: only before the first chunk"); return 1; }
-  if (k && (h->lstm_tolerance || cmx_mixnet_mode(h->mix) == 1)) { cmx_set_err("cmx_pipeline_set_lstm_shadow: the tolerance switch is set (the vote compares strict kernels)"); return 1; }
-  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
-  if (k == h->lstm_shadow) return 0;
-  lstm_shadow_drop(h);
-  if (k == 0) return probe_streams(h) < 0 ? 1 : 0;
-  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) {
-    cmx_set_err("cmx_pipeline_set_lstm_shadow: this process holds " + std::to_string(cmx_hw_queues(h->device)) + " dedicated hardware queues on device " + std::to_string(h->device) +
-                " and " + std::to_string(k) + " shadow LSTM stage(s) need one each, the limit is " + std::to_string(CMX_MAX_HW_QUEUES));
-    return 1;
-  }
-  if (!wg_claim(h, 52 * k, "cmx_pipeline_set_lstm_shadow")) return 1;
-  h->lstm_shadow = k;
-  for (int i = 0; i < k; ++i)
-    if (cmx_make_stream(&h->s_ls[i], 0)) { lstm_shadow_drop(h); return 1; }   // (the factory has said why)
-  return probe_streams(h) < 0 ? 1 : 0;
-}
-// the first begin with shadow LSTM stages: the handles, the vote, the per-slot buffers
-static int lstm_shadow_build(cmx_pipeline* h) {
-  const size_t n = h->max_chunk;
-  h->lsvote = cmx_lstmvote_create(h->device, 1 + h->lstm_shadow);
-  if (!h->lsvote) return 1;
-  for (int i = 0; i < h->lstm_shadow; ++i) {
-    h->ls[i] = cmx_lstm_create(h->vocab, 31, h->device);   // as the stream's own (cmx_pipeline_create)
-    if (!h->ls[i]) return 1;
-  }
-  bool ok = hipSetDevice(h->device) == hipSuccess;
-  for (Slot& s : h->slot) {
-    for (int i = 0; i < h->lstm_shadow; ++i)
-      ok = ok && hipMalloc((void**)&s.d_lsout[i], n * 256 * 4) == hipSuccess && hipMalloc((void**)&s.d_lsp[i], 8 * n * 4) == hipSuccess &&
-           hipMalloc((void**)&s.d_lsex[i], 8 * n * 4) == hipSuccess && hipEventCreateWithFlags(&s.ev_ls[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_lsvote, 14 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_lsvote, hipEventDisableTiming) == hipSuccess;
-    if (ok) memset(s.h_lsvote, 0, 14 * 8);
-  }
-  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_begin: buffer allocation for the shadow LSTM stages failed"); return 1; }
-  return 0;
-}
-int cmx_pipeline_lstm_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) {
-  if (!h || !out) { cmx_set_err("cmx_pipeline_lstm_shadow_report: bad argument"); return 1; }
-  if (!h->lsvote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
-  return cmx_lstmvote_report(h->lsvote, out);
+  void* v;
+  if (shadow_values_guard(h, SH_CTX, words, 3 * CMX_CTXVOTE_COLS, &v)) return 1;
+  if (!v) { if (bit) *bit = 0; return 0; }
+  return cmx_ctxvote_values((cmx_ctxvote_t*)v, words, bit);
 }
 int cmx_pipeline_lstm_shadow_values(cmx_pipeline_t* h, uint32_t words[3 * CMX_LSTMVOTE_COLS], uint32_t* byte) {
-  if (!h || !words) { cmx_set_err("cmx_pipeline_lstm_shadow_values: bad argument"); return 1; }
-  if (!h->lsvote) { memset(words, 0, 3 * CMX_LSTMVOTE_COLS * 4); if (byte) *byte = 0; return 0; }
-  return cmx_lstmvote_values(h->lsvote, words, byte);
-}
-static cmx_lstm_t* lstm_shadow_instance(cmx_pipeline* h, int i) { return i == 0 ? h->lstm : i > 0 && i <= h->lstm_shadow ? h->ls[i - 1] : nullptr; }
-int cmx_pipeline_lstm_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[16]) {
-  if (!h || !out) { cmx_set_err("cmx_pipeline_lstm_shadow_state_diff: bad argument"); return 1; }
-  cmx_lstm_t *x = lstm_shadow_instance(h, a), *y = lstm_shadow_instance(h, b);
-  if (!x || !y) { cmx_set_err("cmx_pipeline_lstm_shadow_state_diff: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
-  return cmx_lstm_state_diff(x, y, out);
-}
-int cmx_pipeline_debug_lstm_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t index, uint32_t xor_mask) {
-  if (!h) { cmx_set_err("cmx_pipeline_debug_lstm_shadow_xor: null handle"); return 1; }
-  cmx_lstm_t* x = lstm_shadow_instance(h, instance);
-  if (!x) { cmx_set_err("cmx_pipeline_debug_lstm_shadow_xor: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk on)"); return 1; }
-  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_lstm_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
-  return cmx_lstm_debug_state_xor(x, region, index, xor_mask);
-}
-// ---- shadow fxcm stages and their vote (include/cmix_amd.h; fxcm_vote.hip) ----
-// Reserves here what can be refused -- k streams of the factory (the queue budget) and 4 resident workgroups per shadow --; the k handles (4.4 GB
-// each, no parser), the vote and the per-slot row buffers are made at the first begin or at pretrain, whichever comes first. Refused after
-// cmx_pipeline_pretrain: fxcm IS pretrained (predictor.cpp:471-476) and a shadow made now would have missed the dictionary.
-int cmx_pipeline_set_fxcm_shadow(cmx_pipeline_t* h, int k) {
-  if (!h) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: null handle"); return 1; }
-  if (k < 0 || k > 2) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: k must be 0, 1 or 2 shadow fxcm stages (a vote has 2 or 3 instances)"); return 1; }
-  if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: only before the first chunk"); return 1; }
-  if (k && !h->fxcm) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: the fxcm stage is not on the device (cmx_pipeline_enable_fxcm first)"); return 1; }
-  if (k && h->pretrained && k != h->fxcm_shadow) { cmx_set_err("cmx_pipeline_set_fxcm_shadow: only before cmx_pipeline_pretrain (fxcm learns the dictionary: a shadow made now would have missed it)"); return 1; }
-  if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
-  if (k == h->fxcm_shadow) return 0;
-  fxcm_shadow_drop(h);
-  if (k == 0) return probe_streams(h) < 0 ? 1 : 0;
-  if (cmx_hw_queues(h->device) + k > CMX_MAX_HW_QUEUES) {
-    cmx_set_err("cmx_pipeline_set_fxcm_shadow: this process holds " + std::to_string(cmx_hw_queues(h->device)) + " dedicated hardware queues on device " + std::to_string(h->device) +
-                " and " + std::to_string(k) + " shadow fxcm stage(s) need one each, the limit is " + std::to_string(CMX_MAX_HW_QUEUES));
-    return 1;
-  }
-  if (!wg_claim(h, 4 * k, "cmx_pipeline_set_fxcm_shadow")) return 1;
-  h->fxcm_shadow = k;
-  for (int i = 0; i < k; ++i)
-    if (cmx_make_stream(&h->s_fs[i], 0)) { fxcm_shadow_drop(h); return 1; }   // (the factory has said why)
-  return probe_streams(h) < 0 ? 1 : 0;
-}
-// the first begin (or pretrain) with shadow fxcm stages: the handles, the vote, the per-slot buffers, the pretraining scratch
-static int fxcm_shadow_build(cmx_pipeline* h) {
-  const size_t n = h->max_chunk;
-  h->fsvote = cmx_fxcmvote_create(h->device, 1 + h->fxcm_shadow);
-  if (!h->fsvote) return 1;
-  for (int i = 0; i < h->fxcm_shadow; ++i) {
-    h->fs[i] = cmx_fxcm_create_shadow(h->device);
-    if (!h->fs[i]) return 1;
-  }
-  bool ok = hipSetDevice(h->device) == hipSuccess;
-  for (Slot& s : h->slot) {
-    for (int i = 0; i < h->fxcm_shadow; ++i)
-      ok = ok && hipMalloc((void**)&s.d_fsp[i], 8 * n * 434 * sizeof(float)) == hipSuccess && hipEventCreateWithFlags(&s.ev_fs[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_fsvote, 14 * 8, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&s.ev_fsvote, hipEventDisableTiming) == hipSuccess;
-    if (ok) memset(s.h_fsvote, 0, 14 * 8);
-  }
-  if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_pipeline_begin: buffer allocation for the shadow fxcm stages failed"); return 1; }
-  return 0;
-}
-int cmx_pipeline_fxcm_shadow_report(cmx_pipeline_t* h, uint64_t out[8]) {
-  if (!h || !out) { cmx_set_err("cmx_pipeline_fxcm_shadow_report: bad argument"); return 1; }
-  if (!h->fsvote) { memset(out, 0, 8 * sizeof(uint64_t)); return 0; }
-  return cmx_fxcmvote_report(h->fsvote, out);
+  void* v;
+  if (shadow_values_guard(h, SH_LSTM, words, 3 * CMX_LSTMVOTE_COLS, &v)) return 1;
+  if (!v) { if (byte) *byte = 0; return 0; }
+  return cmx_lstmvote_values((cmx_lstmvote_t*)v, words, byte);
 }
 int cmx_pipeline_fxcm_shadow_values(cmx_pipeline_t* h, uint32_t words[3 * CMX_FXCMVOTE_COLS], uint32_t* bit, uint32_t* byte) {
-  if (!h || !words) { cmx_set_err("cmx_pipeline_fxcm_shadow_values: bad argument"); return 1; }
-  if (!h->fsvote) { memset(words, 0, 3 * CMX_FXCMVOTE_COLS * 4); if (bit) *bit = 0; if (byte) *byte = 0; return 0; }
-  return cmx_fxcmvote_values(h->fsvote, words, bit, byte);
+  void* v;
+  if (shadow_values_guard(h, SH_FXCM, words, 3 * CMX_FXCMVOTE_COLS, &v)) return 1;
+  if (!v) { if (bit) *bit = 0; if (byte) *byte = 0; return 0; }
+  return cmx_fxcmvote_values((cmx_fxcmvote_t*)v, words, bit, byte);
 }
-static cmx_fxcm_t* fxcm_shadow_instance(cmx_pipeline* h, int i) { return i == 0 ? h->fxcm : i > 0 && i <= h->fxcm_shadow ? h->fs[i - 1] : nullptr; }
-int cmx_pipeline_fxcm_shadow_state_diff(cmx_pipeline_t* h, int a, int b, uint64_t out[CMX_FXCM_STATE_OUT]) {
-  if (!h || !out) { cmx_set_err("cmx_pipeline_fxcm_shadow_state_diff: bad argument"); return 1; }
-  cmx_fxcm_t *x = fxcm_shadow_instance(h, a), *y = fxcm_shadow_instance(h, b);
-  if (!x || !y) { cmx_set_err("cmx_pipeline_fxcm_shadow_state_diff: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk or pretrain on)"); return 1; }
-  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_fxcm_shadow_state_diff: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
-  return cmx_fxcm_state_diff(x, y, out);
+int cmx_pipeline_debug_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
+  void* x = shadow_xor_instance(h, SH_MIX, instance);
+  return x ? cmx_mixnet_debug_state_xor((cmx_mixnet_t*)x, region, mixer, row, index, xor_mask) : 1;
+}
+int cmx_pipeline_debug_ctx_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t lane, uint64_t index, uint32_t xor_mask) {
+  void* x = shadow_xor_instance(h, SH_CTX, instance);
+  return x ? cmx_ctxmodels_debug_state_xor((cmx_ctxmodels_t*)x, region, lane, index, xor_mask) : 1;
+}
+int cmx_pipeline_debug_lstm_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t index, uint32_t xor_mask) {
+  void* x = shadow_xor_instance(h, SH_LSTM, instance);
+  return x ? cmx_lstm_debug_state_xor((cmx_lstm_t*)x, region, index, xor_mask) : 1;
 }
 int cmx_pipeline_debug_fxcm_shadow_xor(cmx_pipeline_t* h, int instance, int region, uint64_t index, uint32_t xor_mask) {
-  if (!h) { cmx_set_err("cmx_pipeline_debug_fxcm_shadow_xor: null handle"); return 1; }
-  cmx_fxcm_t* x = fxcm_shadow_instance(h, instance);
-  if (!x) { cmx_set_err("cmx_pipeline_debug_fxcm_shadow_xor: no such instance (0 = the stream's own stage, 1.. = the shadows, which exist from the first chunk or pretrain on)"); return 1; }
-  if (h->finished != h->chunks) { cmx_set_err("cmx_pipeline_debug_fxcm_shadow_xor: between chunks only (a begun chunk is waiting for cmx_pipeline_finish)"); return 1; }
-  return cmx_fxcm_debug_state_xor(x, region, index, xor_mask);
+  void* x = shadow_xor_instance(h, SH_FXCM, instance);
+  return x ? cmx_fxcm_debug_state_xor((cmx_fxcm_t*)x, region, index, xor_mask) : 1;
 }
 // 0 strict, 1 tolerance: not strict as soon as EITHER the mixing network or the LSTM computes in its tolerance form
 int cmx_pipeline_stage_overlap(cmx_pipeline_t* h) { return h ? h->overlap : -1; }
@@ -1042,7 +827,7 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
   if (h->chunks - h->finished >= (uint64_t)kSlots) { cmx_set_err("cmx_pipeline_begin: too many chunks begun and not finished"); return 1; }
   if (h->failed) { cmx_set_err("cmx_pipeline_begin: an earlier chunk of this handle failed part-way; its state is void (destroy it)"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
-  struct Txn { cmx_pipeline* h; bool ok = false; ~Txn() { if (!ok) h->failed = true; } } txn{h};   // from here on a failure leaves stages half-enqueued
+  ChunkTxn txn{h};   // from here on a failure leaves stages half-enqueued
   Slot& s = h->slot[h->chunks % kSlots];
   auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_mark = now();
@@ -1081,28 +866,18 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
   if (cmx_bytemodel_bits_run(h->device, s.d_ppmd, s.d_ppmd + 256, s.d_bytes, n, d_layer0 + 2076, CMX_N_INPUTS, nullptr,
                              h->s_ctx)) return 1;
   (void)hipEventRecord(s.ev_ctx1, h->s_ctx);
-  if (h->ctx_shadow) {   // ---- the same bytes on every shadow context stage, into buffers of its own; then the vote on the last shadow's stream ----
-    if (!h->cxvote && ctx_shadow_build(h)) return 1;
-    const int k = h->ctx_shadow;
-    const float* vp[3] = {d_layer0, nullptr, nullptr};
-    const uint32_t* vs[3] = {s.d_sel, nullptr, nullptr};
-    const size_t stride[3] = {CMX_N_INPUTS, CMX_CTX_COMPACT_STRIDE, CMX_CTX_COMPACT_STRIDE};
-    const int compact[3] = {0, 1, 1};
-    for (int i = 0; i < k; ++i) {
-      hipStream_t q = h->s_cx[i];
-      (void)hipStreamWaitEvent(q, s.ev_in, 0);
-      if (cmx_ctxmodels_run(h->cx[i], s.d_bytes, n, s.d_cxp[i], CMX_CTX_COMPACT_STRIDE, s.d_cxsel[i], q)) return 1;
-      (void)hipEventRecord(s.ev_cx[i], q);
-      vp[i + 1] = s.d_cxp[i]; vs[i + 1] = s.d_cxsel[i];
-    }
-    hipStream_t q = h->s_cx[k - 1];
-    (void)hipStreamWaitEvent(q, s.ev_ctx1, 0);
-    for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_cx[i], 0);
-    if (cmx_ctxvote_run(h->cxvote, vp, stride, compact, vs, 8 * n, h->cxvote_bits, s.d_bits, q)) return 1;
-    (void)hipMemcpyAsync(s.h_cxvote, cmx_ctxvote_record(h->cxvote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
-    (void)hipEventRecord(s.ev_cxvote, q);
-    s.cxvoted = true;
-    h->cxvote_bits += 8 * n;
+  if (const ShadowSet& S = h->sh[SH_CTX]; S.k) {   // ---- the same bytes on every shadow context stage (compact form) ----
+    void* const(&d)[2][3] = s.sh[SH_CTX].d;   // a shadow's model outputs, its selectors (there once shadow_chunk has built them; an absent shadow's stay null)
+    if (shadow_chunk(h, kShadow[SH_CTX], s, {s.ev_in}, s.ev_ctx1, 8 * n,
+                     [&](int i, hipStream_t q) { return cmx_ctxmodels_run((cmx_ctxmodels_t*)S.inst[i], s.d_bytes, n, (float*)d[i][0], CMX_CTX_COMPACT_STRIDE, (uint32_t*)d[i][1], q); },
+                     [&](hipStream_t q, uint64_t bit0) {
+                       const float* vp[3] = {d_layer0, (float*)d[0][0], (float*)d[1][0]};
+                       const uint32_t* vs[3] = {s.d_sel, (uint32_t*)d[0][1], (uint32_t*)d[1][1]};
+                       const size_t stride[3] = {CMX_N_INPUTS, CMX_CTX_COMPACT_STRIDE, CMX_CTX_COMPACT_STRIDE};
+                       const int compact[3] = {0, 1, 1};
+                       return cmx_ctxvote_run((cmx_ctxvote_t*)S.vote, vp, stride, compact, vs, 8 * n, bit0, s.d_bits, q);
+                     }))
+      return 1;
   }
   // ---- LSTM byte mixer ----
   (void)hipEventRecord(s.ev_lstm0, h->s_lstm);
@@ -1112,30 +887,18 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
   // the stage's sticky time-out flag, in stream order behind its kernels: cmx_pipeline_wait looks at it per chunk
   (void)hipMemcpyAsync(&s.h_fail[0], cmx_lstm_fail_flag(h->lstm), 4, hipMemcpyDeviceToHost, h->s_lstm);
   (void)hipEventRecord(s.ev_lstm1, h->s_lstm);
-  if (h->lstm_shadow) {   // ---- the same bytes and PPMd distributions (both behind ev_in) on every shadow LSTM stage, into buffers of its own; then the vote on the last shadow's stream ----
-    if (!h->lsvote && lstm_shadow_build(h)) return 1;   // (nothing downstream of the stream's own stage waits for any of this)
-    const int k = h->lstm_shadow;
-    int* const ex0 = (int*)(s.d_hint + (8 * h->max_chunk + 1));
-    const float* vd[3] = {s.d_lstm_out, nullptr, nullptr};
-    const float* vp[3] = {d_layer0 + 2077, nullptr, nullptr};
-    const int* vx[3] = {ex0, nullptr, nullptr};
-    const size_t stride[3] = {CMX_N_INPUTS, 1, 1};
-    for (int i = 0; i < k; ++i) {
-      hipStream_t q = h->s_ls[i];
-      (void)hipStreamWaitEvent(q, s.ev_in, 0);
-      if (cmx_lstm_run(h->ls[i], s.d_ppmd + 256, s.d_bytes, n, s.d_lsout[i], s.d_lsp[i], 1, s.d_lsex[i], q)) return 1;
-      (void)hipMemcpyAsync((unsigned*)(s.h_lsvote + 12) + i, cmx_lstm_fail_flag(h->ls[i]), 4, hipMemcpyDeviceToHost, q);
-      (void)hipEventRecord(s.ev_ls[i], q);
-      vd[i + 1] = s.d_lsout[i]; vp[i + 1] = s.d_lsp[i]; vx[i + 1] = s.d_lsex[i];
-    }
-    hipStream_t q = h->s_ls[k - 1];
-    (void)hipStreamWaitEvent(q, s.ev_lstm1, 0);
-    for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_ls[i], 0);
-    if (cmx_lstmvote_run(h->lsvote, vd, vp, stride, vx, n, h->lsvote_bytes, s.d_bytes, q)) return 1;
-    (void)hipMemcpyAsync(s.h_lsvote, cmx_lstmvote_record(h->lsvote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
-    (void)hipEventRecord(s.ev_lsvote, q);
-    s.lsvoted = true;
-    h->lsvote_bytes += n;
+  if (const ShadowSet& S = h->sh[SH_LSTM]; S.k) {   // ---- the same bytes and PPMd distributions (both behind ev_in) on every shadow LSTM stage; its vote counts bytes ----
+    void* const(&d)[2][3] = s.sh[SH_LSTM].d;   // a shadow's distributions, its bit predictions (dense), its ex
+    if (shadow_chunk(h, kShadow[SH_LSTM], s, {s.ev_in}, s.ev_lstm1, n,
+                     [&](int i, hipStream_t q) { return cmx_lstm_run((cmx_lstm_t*)S.inst[i], s.d_ppmd + 256, s.d_bytes, n, (float*)d[i][0], (float*)d[i][1], 1, (int*)d[i][2], q); },
+                     [&](hipStream_t q, uint64_t byte0) {
+                       const float* vd[3] = {s.d_lstm_out, (float*)d[0][0], (float*)d[1][0]};
+                       const float* vp[3] = {d_layer0 + 2077, (float*)d[0][1], (float*)d[1][1]};
+                       const int* vx[3] = {(int*)(s.d_hint + (8 * h->max_chunk + 1)), (int*)d[0][2], (int*)d[1][2]};
+                       const size_t stride[3] = {CMX_N_INPUTS, 1, 1};
+                       return cmx_lstmvote_run((cmx_lstmvote_t*)S.vote, vd, vp, stride, vx, n, byte0, s.d_bytes, q);
+                     }))
+      return 1;
   }
   lap(2);
   if (h->fxcm) {  // ---- fxcm stage: hints from the LSTM's columns, then the parser (this thread) and the kernel on its own stream ----
@@ -1151,27 +914,17 @@ int cmx_pipeline_begin(cmx_pipeline_t* h, const uint8_t* bytes, size_t n, float*
     if (cmx_fxcm_run(h->fxcm, bytes, s.d_bytes, n, s.d_fx_pr, s.d_fx_ex, d_layer0, CMX_N_INPUTS, h->s_fx)) return 1;
     (void)hipMemcpyAsync(&s.h_fail[1], cmx_fxcm_fail_flag(h->fxcm), 4, hipMemcpyDeviceToHost, h->s_fx);
     (void)hipEventRecord(s.ev_fx1, h->s_fx);
-    if (h->fxcm_shadow) {   // ---- the same records, bytes and hints on every shadow fxcm stage, into rows of its own; then the vote on the last shadow's stream ----
-      if (!h->fsvote && fxcm_shadow_build(h)) return 1;   // (nothing downstream of the stream's own stage waits for any of this)
-      const int k = h->fxcm_shadow;
-      const float* vr[3] = {d_layer0 + 3, nullptr, nullptr};
-      const size_t stride[3] = {CMX_N_INPUTS, 434, 434};
-      for (int i = 0; i < k; ++i) {
-        hipStream_t q = h->s_fs[i];
-        (void)hipStreamWaitEvent(q, s.ev_fxin, 0);   // the hints (behind the bytes' upload); cmx_fxcm_run_shared adds the wait for the records' upload
-        if (cmx_fxcm_run_shared(h->fs[i], h->fxcm, s.d_bytes, n, s.d_fx_pr, s.d_fx_ex, s.d_fsp[i], 434, q)) return 1;
-        (void)hipMemcpyAsync((unsigned*)(s.h_fsvote + 12) + i, cmx_fxcm_fail_flag(h->fs[i]), 4, hipMemcpyDeviceToHost, q);
-        (void)hipEventRecord(s.ev_fs[i], q);
-        vr[i + 1] = s.d_fsp[i] + 3;
-      }
-      hipStream_t q = h->s_fs[k - 1];
-      (void)hipStreamWaitEvent(q, s.ev_fx1, 0);
-      for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_fs[i], 0);
-      if (cmx_fxcmvote_run(h->fsvote, vr, stride, T, h->fsvote_bits, s.d_bytes, q)) return 1;
-      (void)hipMemcpyAsync(s.h_fsvote, cmx_fxcmvote_record(h->fsvote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
-      (void)hipEventRecord(s.ev_fsvote, q);
-      s.fsvoted = true;
-      h->fsvote_bits += T;
+    if (const ShadowSet& S = h->sh[SH_FXCM]; S.k) {   // ---- the same records, bytes and hints on every shadow fxcm stage, into rows of its own ----
+      void* const(&d)[2][3] = s.sh[SH_FXCM].d;   // a shadow's rows
+      // every shadow waits for the hints (behind the bytes' upload); cmx_fxcm_run_shared adds the wait for the records' upload
+      if (shadow_chunk(h, kShadow[SH_FXCM], s, {s.ev_fxin}, s.ev_fx1, T,
+                       [&](int i, hipStream_t q) { return cmx_fxcm_run_shared((cmx_fxcm_t*)S.inst[i], h->fxcm, s.d_bytes, n, s.d_fx_pr, s.d_fx_ex, (float*)d[i][0], 434, q); },
+                       [&](hipStream_t q, uint64_t bit0) {
+                         const float* vr[3] = {d_layer0 + 3, (float*)d[0][0] + 3, d[1][0] ? (float*)d[1][0] + 3 : nullptr};
+                         const size_t stride[3] = {CMX_N_INPUTS, 434, 434};
+                         return cmx_fxcmvote_run((cmx_fxcmvote_t*)S.vote, vr, stride, T, bit0, s.d_bytes, q);
+                       }))
+        return 1;
     }
   }
   lap(3);
@@ -1236,7 +989,7 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
   if (h->finished >= h->chunks) { cmx_set_err("cmx_pipeline_finish: no begun chunk"); return 1; }
   if (h->failed) { cmx_set_err("cmx_pipeline_finish: an earlier chunk of this handle failed part-way; its state is void (destroy it)"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
-  struct Txn { cmx_pipeline* h; bool ok = false; ~Txn() { if (!ok) h->failed = true; } } txn{h};
+  ChunkTxn txn{h};
   Slot& s = h->slot[h->finished % kSlots];
   const size_t n = s.n;
   if (cols) {  // returns once the rows have been read: the caller may reuse `cols` right away
@@ -1255,8 +1008,9 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
   float* dmix = nullptr;
   if (h->dbg_mix && h->dbg_mix_bits + 8 * n <= h->dbg_mix_cap) dmix = h->dbg_mix + h->dbg_mix_bits * 47;   // (CMX_MIXERS, mixnet_state.h)
   h->dbg_mix_bits += 8 * n;
-  if (h->shadow && !h->vote && shadow_build(h)) return 1;
-  if (h->shadow && !dmix) dmix = s.d_shmix[0];   // the vote compares every instance's 47 mixer outputs
+  const ShadowSet& S = h->sh[SH_MIX];
+  if (S.k && !S.vote && shadow_build(h, kShadow[SH_MIX])) return 1;   // (here, not at the vote: the stream's own network writes into a buffer of it)
+  if (S.k && !dmix) dmix = (float*)s.sh[SH_MIX].d_own;   // the vote compares every instance's 47 mixer outputs
   if (cmx_mixnet_run(h->mix, s.d_layer0, s.d_sel, s.d_bits, 8 * n, d_p_out, dmix, h->s_mix)) return 1;
   // the kernel's sticky time-out word, in stream order behind it: cmx_pipeline_wait looks at it per chunk (a look-ahead coder never
   // calls cmx_pipeline_sync, the only other place where it is read)
@@ -1270,30 +1024,16 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
     s.journalled = true;
     h->jr_bits += 8 * n;
   }
-  if (h->shadow) {   // ---- the same chunk on every shadow, from the slot's own rows / selectors / bits; then the vote on the last shadow's stream ----
-    const float* vp[3] = {d_p_out, nullptr, nullptr};
-    const float* vm[3] = {dmix, nullptr, nullptr};
-    const int k = h->shadow;
-    for (int i = 0; i < k; ++i) {
-      hipStream_t q = h->s_sh[i];
-      (void)hipStreamWaitEvent(q, s.ev_ctx1, 0);
-      (void)hipStreamWaitEvent(q, s.ev_lstm1, 0);
-      if (h->fxcm) (void)hipStreamWaitEvent(q, s.ev_fx1, 0);
-      if (h->p8) (void)hipStreamWaitEvent(q, s.ev_p81, 0);
-      if (cols) (void)hipStreamWaitEvent(q, s.ev_cols, 0);
-      if (cmx_mixnet_run(h->sh[i], s.d_layer0, s.d_sel, s.d_bits, 8 * n, s.d_shp[i], s.d_shmix[i + 1], q)) return 1;
-      (void)hipMemcpyAsync((unsigned*)(s.h_vote + 12) + i, cmx_mixnet_error_flag(h->sh[i]), 4, hipMemcpyDeviceToHost, q);
-      (void)hipEventRecord(s.ev_sh[i], q);
-      vp[i + 1] = s.d_shp[i]; vm[i + 1] = s.d_shmix[i + 1];
-    }
-    hipStream_t q = h->s_sh[k - 1];
-    (void)hipStreamWaitEvent(q, s.ev_mix1, 0);
-    for (int i = 0; i + 1 < k; ++i) (void)hipStreamWaitEvent(q, s.ev_sh[i], 0);
-    if (cmx_vote_run(h->vote, vp, vm, 8 * n, h->vote_bits, s.d_sel, s.d_bits, q)) return 1;
-    (void)hipMemcpyAsync(s.h_vote, cmx_vote_record(h->vote), 96, hipMemcpyDeviceToHost, q);   // the record and, right behind it, this chunk's own result
-    (void)hipEventRecord(s.ev_vote, q);
-    s.voted = true;
-    h->vote_bits += 8 * n;
+  if (S.k) {   // ---- the same chunk on every shadow, from the slot's own rows / selectors / bits: behind every producer of them ----
+    void* const(&d)[2][3] = s.sh[SH_MIX].d;   // a shadow's p, its mixer outputs
+    if (shadow_chunk(h, kShadow[SH_MIX], s, {s.ev_ctx1, s.ev_lstm1, h->fxcm ? s.ev_fx1 : nullptr, h->p8 ? s.ev_p81 : nullptr, cols ? s.ev_cols : nullptr}, s.ev_mix1, 8 * n,
+                     [&](int i, hipStream_t q) { return cmx_mixnet_run((cmx_mixnet_t*)S.inst[i], s.d_layer0, s.d_sel, s.d_bits, 8 * n, (float*)d[i][0], (float*)d[i][1], q); },
+                     [&](hipStream_t q, uint64_t bit0) {
+                       const float* vp[3] = {d_p_out, (float*)d[0][0], (float*)d[1][0]};
+                       const float* vm[3] = {dmix, (float*)d[0][1], (float*)d[1][1]};
+                       return cmx_vote_run((cmx_vote_t*)S.vote, vp, vm, 8 * n, bit0, s.d_sel, s.d_bits, q);
+                     }))
+      return 1;
   }
   s.d_p = d_p_out;
   s.d_mix0 = dmix;
@@ -1348,8 +1088,9 @@ int cmx_pipeline_pretrain(cmx_pipeline_t* h, const uint8_t* bytes, size_t n) {
   hipEvent_t ev_d = nullptr;   // the dictionary bytes are on the device before the fxcm kernels read them
   ok = ok && hipEventCreateWithFlags(&ev_d, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev_d, h->s_ctx) == hipSuccess;
   ok = ok && cmx_ctxmodels_pretrain(h->ctx, d, n, h->s_ctx) == 0;
-  if (ok && h->ctx_shadow && !h->cxvote) ok = ctx_shadow_build(h) == 0;   // every shadow context stage learns the same bytes
-  for (int i = 0; ok && i < h->ctx_shadow; ++i) ok = hipStreamWaitEvent(h->s_cx[i], ev_d, 0) == hipSuccess && cmx_ctxmodels_pretrain(h->cx[i], d, n, h->s_cx[i]) == 0;
+  ShadowSet &CX = h->sh[SH_CTX], &FS = h->sh[SH_FXCM];
+  if (ok && CX.k && !CX.vote) ok = shadow_build(h, kShadow[SH_CTX]) == 0;   // every shadow context stage learns the same bytes
+  for (int i = 0; ok && i < CX.k; ++i) ok = hipStreamWaitEvent(CX.q[i], ev_d, 0) == hipSuccess && cmx_ctxmodels_pretrain((cmx_ctxmodels_t*)CX.inst[i], d, n, CX.q[i]) == 0;
   // fxcm and paq8 are two of models_: Predict + Perceive per dictionary bit (predictor.cpp:471-476), fxcm with the hints at their start-up
   // value 0 (:359); the rows are discarded. The three stages learn independently, so their chunks are enqueued side by side (context
   // stage on its stream, fxcm and paq8 chunk by chunk on theirs) and waited for once: the dictionary costs the slowest stage, not the sum.
@@ -1363,24 +1104,24 @@ int cmx_pipeline_pretrain(cmx_pipeline_t* h, const uint8_t* bytes, size_t n) {
   // every shadow fxcm stage learns the dictionary too: each chunk on the shared records with the same zero hints, on its own stream into a scratch of
   // its own; the rows are discarded, nothing is voted
   hipEvent_t ev_z = nullptr;
-  if (ok && h->fxcm && h->fxcm_shadow) {
-    if (!h->fsvote) ok = fxcm_shadow_build(h) == 0;
+  if (ok && h->fxcm && FS.k) {
+    if (!FS.vote) ok = shadow_build(h, kShadow[SH_FXCM]) == 0;
     ok = ok && hipEventCreateWithFlags(&ev_z, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev_z, h->s_fx) == hipSuccess;   // behind the hints' memsets and ev_d
-    for (int i = 0; ok && i < h->fxcm_shadow; ++i) {
-      if (!h->d_fs_scratch[i]) ok = hipMalloc((void**)&h->d_fs_scratch[i], 8 * C * 434 * sizeof(float)) == hipSuccess;
-      ok = ok && hipStreamWaitEvent(h->s_fs[i], ev_z, 0) == hipSuccess;
+    for (int i = 0; ok && i < FS.k; ++i) {
+      if (!FS.d_scratch[i]) ok = hipMalloc((void**)&FS.d_scratch[i], 8 * C * 434 * sizeof(float)) == hipSuccess;
+      ok = ok && hipStreamWaitEvent(FS.q[i], ev_z, 0) == hipSuccess;
     }
   }
   for (size_t off = 0; ok && off < n; off += C) {
     const size_t m = n - off < C ? n - off : C;
     if (h->fxcm) ok = cmx_fxcm_run(h->fxcm, bytes + off, d + off, m, zpr, zex, h->d_fx_scratch, 434, h->s_fx) == 0;
-    for (int i = 0; ok && h->fxcm && i < h->fxcm_shadow; ++i) ok = cmx_fxcm_run_shared(h->fs[i], h->fxcm, d + off, m, zpr, zex, h->d_fs_scratch[i], 434, h->s_fs[i]) == 0;
+    for (int i = 0; ok && h->fxcm && i < FS.k; ++i) ok = cmx_fxcm_run_shared((cmx_fxcm_t*)FS.inst[i], h->fxcm, d + off, m, zpr, zex, FS.d_scratch[i], 434, FS.q[i]) == 0;
     if (ok && h->p8) ok = cmx_p8stage_run(h->p8, bytes + off, m, h->d_p8_scratch, 1591, h->s_p8) == 0;
   }
   ok = hipStreamSynchronize(h->s_ctx) == hipSuccess && ok;
-  for (hipStream_t q : h->s_cx) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (h->fxcm) ok = hipStreamSynchronize(h->s_fx) == hipSuccess && ok;
-  for (hipStream_t q : h->s_fs) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
+  for (const ShadowKind& K : kShadow)   // the shadows of the stages that learn the dictionary
+    for (hipStream_t q : h->sh[K.id].q) if (K.pretrained && q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (ev_z) (void)hipEventDestroy(ev_z);
   if (h->p8) ok = hipStreamSynchronize(h->s_p8) == hipSuccess && ok;
   h->pretrained = true;
@@ -1451,8 +1192,8 @@ int cmx_pipeline_set_shadow_repair(cmx_pipeline_t* h, int max_repairs) {
   if (!h) { cmx_set_err("cmx_pipeline_set_shadow_repair: null handle"); return 1; }
   if (max_repairs < 0) { cmx_set_err("cmx_pipeline_set_shadow_repair: max_repairs must be 0 (off) or the number of repairs allowed"); return 1; }
   if (h->chunks || h->late) { cmx_set_err("cmx_pipeline_set_shadow_repair: only before the first chunk"); return 1; }
-  if (max_repairs && h->shadow != 2) {
-    cmx_set_err("cmx_pipeline_set_shadow_repair: repair needs 2 shadow mixing networks (cmx_pipeline_set_shadow(2) first): a vote of " + std::to_string(1 + h->shadow) +
+  if (max_repairs && h->sh[SH_MIX].k != 2) {
+    cmx_set_err("cmx_pipeline_set_shadow_repair: repair needs 2 shadow mixing networks (cmx_pipeline_set_shadow(2) first): a vote of " + std::to_string(1 + h->sh[SH_MIX].k) +
                 " instance(s) has no majority to continue on");
     return 1;
   }
@@ -1477,10 +1218,11 @@ int cmx_pipeline_shadow_repairs(cmx_pipeline_t* h, uint64_t out[], size_t cap) {
 // majority and, where the odd instance is the stream's own network, replaces the outputs of the chunks it ran past the event. 0: repaired.
 static int shadow_repair(cmx_pipeline* h, uint64_t index) {
   const Slot& sw = h->slot[index % kSlots];
-  auto stop = [&](const unsigned long long* event) {   // today's message (the sticky record), the repairs before it, and -- where it is not the record's -- this event
-    std::string m = "cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + vote_text(sw.h_vote) + repairs_text(h);
+  const ShadowSet& S = h->sh[SH_MIX];
+  auto stop = [&](const uint64_t* event) {   // today's message (the sticky record), the repairs before it, and -- where it is not the record's -- this event
+    std::string m = "cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + shadow_vote_text(SH_MIX, sw.sh[SH_MIX].rec) + repairs_text(h);
     if (h->repairs && event)
-      m += "; not repaired: stream bit " + std::to_string(event[1]) + ", " + (event[2] < 47 ? "mixer " + std::to_string(event[2]) : std::string("final p")) + ", " +
+      m += "; not repaired: stream bit " + std::to_string(event[1]) + shadow_where_mix(0, event[2]) + ", " +
            (event[3] == ~0ull ? std::string("no majority") : "instance " + std::to_string(event[3]) + " odd");
     cmx_set_err(m);
     h->failed = true;
@@ -1491,26 +1233,26 @@ static int shadow_repair(cmx_pipeline* h, uint64_t index) {
   bool ok = true;
   for (uint64_t c = lo; c < h->finished; ++c) ok = slot_done(h->slot[c % kSlots]) == hipSuccess && ok;
   ok = hipStreamSynchronize(h->s_mix) == hipSuccess && ok;
-  for (hipStream_t q : h->s_sh) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
+  for (hipStream_t q : S.q) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (!ok) { cmx_set_err("cmx_pipeline_wait: device error while draining for a repair"); h->failed = true; return 1; }
   // 2. / 3. every chunk in flight: agree, or the same odd instance; no time-out of a shadow; the sticky count accounted for; budget left
   uint64_t odd = ~0ull, first = ~0ull, events = 0;
   for (uint64_t c = lo; c < h->finished; ++c) {
-    const Slot& s = h->slot[c % kSlots];
-    const unsigned* shfail = (const unsigned*)(s.h_vote + 12);
-    const unsigned long long* last = s.h_vote + 8;
-    if (!s.voted || shfail[0] || shfail[1]) return stop(nullptr);
+    const ShadowSlot& w = h->slot[c % kSlots].sh[SH_MIX];
+    const unsigned* shfail = (const unsigned*)(w.rec + 12);
+    const uint64_t* last = w.rec + 8;
+    if (!w.voted || shfail[0] || shfail[1]) return stop(nullptr);
     if (!last[0]) continue;
     if (last[3] == ~0ull || (odd != ~0ull && last[3] != odd)) return stop(last);
     if (first == ~0ull) { first = c; odd = last[3]; }
     ++events;
   }
-  const Slot& newest = h->slot[(h->finished - 1) % kSlots];
-  if (first == ~0ull || newest.h_vote[3] != h->repaired_events + events) return stop(nullptr);   // an event in a chunk whose slot has been reused: its result is gone
-  const unsigned long long* ev = h->slot[first % kSlots].h_vote + 8;
+  const ShadowSlot& newest = h->slot[(h->finished - 1) % kSlots].sh[SH_MIX];
+  if (first == ~0ull || newest.rec[3] != h->repaired_events + events) return stop(nullptr);   // an event in a chunk whose slot has been reused: its result is gone
+  const uint64_t* ev = h->slot[first % kSlots].sh[SH_MIX].rec + 8;
   if (h->repairs >= (uint64_t)h->repair_max) return stop(ev);
   // 4. the odd instance's state from a member of the majority
-  cmx_mixnet_t* inst[3] = {h->mix, h->sh[0], h->sh[1]};
+  cmx_mixnet_t* inst[3] = {h->mix, (cmx_mixnet_t*)S.inst[0], (cmx_mixnet_t*)S.inst[1]};
   uint64_t out[20];
   if (cmx_mixnet_state_repair(inst[odd], inst[odd == 0 ? 1 : 0], out)) { h->failed = true; return 1; }
   // 5. the stream's own network was the odd one: the caller's p (and the debug area's mixer outputs) of every chunk it got wrong, from shadow 1.
@@ -1518,9 +1260,10 @@ static int shadow_repair(cmx_pipeline* h, uint64_t index) {
   if (odd == 0) {
     for (uint64_t c = lo; ok && c < h->finished; ++c) {
       const Slot& s = h->slot[c % kSlots];
-      if (!s.h_vote[8]) continue;
-      ok = hipMemcpy(s.d_p, s.d_shp[0], 8 * s.n * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess;
-      if (ok && s.d_mix0 != s.d_shmix[0]) ok = hipMemcpy(s.d_mix0, s.d_shmix[1], 8 * s.n * 47 * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess;
+      const ShadowSlot& w = s.sh[SH_MIX];   // (d[0]: shadow 1's p and its mixer outputs)
+      if (!w.rec[8]) continue;
+      ok = hipMemcpy(s.d_p, w.d[0][0], 8 * s.n * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess;
+      if (ok && s.d_mix0 != w.d_own) ok = hipMemcpy(s.d_mix0, w.d[0][1], 8 * s.n * 47 * sizeof(float), hipMemcpyDeviceToDevice) == hipSuccess;
       if (ok && h->jr && s.journalled) {   // the journal describes the p that is coded: this chunk's partial records again, from the replaced p (everything was drained above)
         if (c < h->jr_folded) { cmx_set_err("cmx_pipeline_wait: a repaired chunk's journal had been folded already (with repair armed every chunk is waited for before its slot is reused)"); h->failed = true; return 1; }
         Slot& w = h->slot[c % kSlots];
@@ -1541,6 +1284,22 @@ static int shadow_repair(cmx_pipeline* h, uint64_t index) {
   h->repaired_events += events;
   h->repaired_upto = h->finished;
   return 0;
+}
+
+// what cmx_pipeline_wait (of chunk `chunk`) and cmx_pipeline_sync (chunk < 0) find behind a kind's shadows. Both return 1, the handle void.
+// An in-launch hand-off of shadow `instance` timed out:
+static int shadow_timed_out(cmx_pipeline* h, ShadowId k, int instance, int64_t chunk) {
+  cmx_set_err(shadow_timeout_text(k, instance, chunk));
+  h->failed = true;
+  return 1;
+}
+// The instances disagreed, in this chunk or an earlier one (the vote's record r is sticky); 0: they have not
+static int shadow_vote_check(cmx_pipeline* h, ShadowId k, const uint64_t r[8], int64_t chunk) {
+  const bool mix = k == SH_MIX;   // the one kind with repair: the events it covered do not count, and a stop behind repairs names them
+  if (r[3] <= (mix ? h->repaired_events : 0)) return 0;
+  cmx_set_err((chunk < 0 ? std::string("cmx_pipeline_sync: ") : "cmx_pipeline_wait: chunk " + std::to_string(chunk) + ": ") + shadow_vote_text(k, r) + (mix ? repairs_text(h) : std::string()));
+  h->failed = true;
+  return 1;
 }
 
 // Wait until chunk number `index` (0 = the first chunk submitted) has left the mixing network: its p[] is complete.
@@ -1566,54 +1325,15 @@ int cmx_pipeline_wait(cmx_pipeline_t* h, uint64_t index) {
     h->failed = true;
     return 1;
   }
-  if (s.lsvoted) {
-    const unsigned* lsfail = (const unsigned*)(s.h_lsvote + 12);
-    if (lsfail[0] || lsfail[1]) {
-      cmx_set_err("cmx_pipeline_wait: an in-launch hand-off of the LSTM kernels of shadow instance " + std::to_string(lsfail[0] ? 1 : 2) +
-                  " timed out (workgroups not co-resident?): the LSTM vote is void from chunk " + std::to_string(index) + " on");
-      h->failed = true;
-      return 1;
-    }
-    if (s.h_lsvote[3]) {   // the LSTM-stage instances disagreed in this chunk or an earlier one (the record is sticky): no repair, the stream stops
-      cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + lstm_vote_text(s.h_lsvote));
-      h->failed = true;
-      return 1;
-    }
-  }
-  if (s.cxvoted && s.h_cxvote[3]) {   // the context-stage instances disagreed in this chunk or an earlier one (the record is sticky): no repair, the stream stops
-    cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + ctx_vote_text(s.h_cxvote));
-    h->failed = true;
-    return 1;
-  }
-  if (s.fsvoted) {
-    const unsigned* fsfail = (const unsigned*)(s.h_fsvote + 12);
-    if (fsfail[0] || fsfail[1]) {
-      cmx_set_err("cmx_pipeline_wait: an in-launch hand-off of the fxcm kernel of shadow instance " + std::to_string(fsfail[0] ? 1 : 2) +
-                  " timed out (workgroups not co-resident?): the fxcm vote is void from chunk " + std::to_string(index) + " on");
-      h->failed = true;
-      return 1;
-    }
-    if (s.h_fsvote[3]) {   // the fxcm-stage instances disagreed in this chunk or an earlier one (the record is sticky): no repair, the stream stops
-      cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + fxcm_vote_text(s.h_fsvote));
-      h->failed = true;
-      return 1;
-    }
-  }
-  if (s.voted) {
-    const unsigned* shfail = (const unsigned*)(s.h_vote + 12);
-    if (shfail[0] || shfail[1]) {
-      cmx_set_err("cmx_pipeline_wait: an in-launch hand-off of shadow mixing network " + std::to_string(shfail[0] ? 1 : 2) + " timed out (workgroups not co-resident?): the vote is void from chunk " +
-                  std::to_string(index) + " on");
-      h->failed = true;
-      return 1;
-    }
-    if (h->repair_max) {   // events beyond those repaired (chunks that an earlier repair drained have their output from the majority already)
-      if (index >= h->repaired_upto && s.h_vote[3] > h->repaired_events && shadow_repair(h, index)) return 1;
-    } else if (s.h_vote[3]) {   // the instances disagreed in this chunk or an earlier one (the record is sticky)
-      cmx_set_err("cmx_pipeline_wait: chunk " + std::to_string(index) + ": " + vote_text(s.h_vote));
-      h->failed = true;
-      return 1;
-    }
+  static const ShadowId order[SH_KINDS] = {SH_LSTM, SH_CTX, SH_FXCM, SH_MIX};   // (kept as it grew: a chunk with two faults goes on naming the same one)
+  for (ShadowId k : order) {
+    const ShadowSlot& w = s.sh[k];
+    if (!w.voted) continue;
+    const unsigned* late = (const unsigned*)(w.rec + 12);   // the shadows' sticky hand-off flags (the context stage's record has none)
+    if (kShadow[k].rec_words > 12 && (late[0] || late[1])) return shadow_timed_out(h, k, late[0] ? 1 : 2, (int64_t)index);
+    if (k == SH_MIX && h->repair_max) {   // events beyond those repaired (chunks that an earlier repair drained have their output from the majority already)
+      if (index >= h->repaired_upto && w.rec[3] > h->repaired_events && shadow_repair(h, index)) return 1;
+    } else if (shadow_vote_check(h, k, w.rec, (int64_t)index)) return 1;   // no repair: the stream stops
   }
   return journal_fold(h, index + 1);   // (behind a repair: a repaired chunk's journal was taken again from the p that is coded)
 }
@@ -1641,43 +1361,19 @@ int cmx_pipeline_sync(cmx_pipeline_t* h) {
   ok = hipStreamSynchronize(h->s_mix) == hipSuccess && ok;
   if (h->s_fx) ok = hipStreamSynchronize(h->s_fx) == hipSuccess && ok;
   if (h->p8) ok = cmx_p8stage_sync(h->p8) == 0 && ok;
-  for (hipStream_t q : h->s_sh) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
-  for (hipStream_t q : h->s_cx) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
-  for (hipStream_t q : h->s_ls) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
-  for (hipStream_t q : h->s_fs) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
+  for (const ShadowSet& S : h->sh)
+    for (hipStream_t q : S.q) if (q) ok = hipStreamSynchronize(q) == hipSuccess && ok;
   if (!ok) { cmx_set_err("cmx_pipeline_sync: device error"); h->failed = true; return 1; }
   if (cmx_ctxmodels_sync(h->ctx) || cmx_mixnet_sync(h->mix)) { h->failed = true; return 1; }
-  for (cmx_ctxmodels_t* c : h->cx) if (c && cmx_ctxmodels_sync(c)) { h->failed = true; return 1; }
-  if (h->cxvote) {
+  for (ShadowId k : kShadowLast) {
+    const ShadowSet& S = h->sh[k];
+    for (int i = 0; i < 2; ++i)
+      if (const int c = S.inst[i] ? kShadow[k].check(S.inst[i]) : 0) {
+        if (c == 2) return shadow_timed_out(h, k, i + 1, -1);
+        h->failed = true; return 1;
+      }
     uint64_t r[8];
-    if (cmx_ctxvote_report(h->cxvote, r)) { h->failed = true; return 1; }
-    if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + ctx_vote_text(t)); h->failed = true; return 1; }
-  }
-  for (int i = 0; i < 2; ++i)
-    if (h->ls[i] && cmx_lstm_failed(h->ls[i])) {
-      cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the LSTM kernels of shadow instance " + std::to_string(i + 1) + " timed out (workgroups not co-resident?): the LSTM vote is void");
-      h->failed = true; return 1;
-    }
-  if (h->lsvote) {
-    uint64_t r[8];
-    if (cmx_lstmvote_report(h->lsvote, r)) { h->failed = true; return 1; }
-    if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + lstm_vote_text(t)); h->failed = true; return 1; }
-  }
-  for (int i = 0; i < 2; ++i)
-    if (h->fs[i] && cmx_fxcm_failed(h->fs[i])) {
-      cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the fxcm kernel of shadow instance " + std::to_string(i + 1) + " timed out (workgroups not co-resident?): the fxcm vote is void");
-      h->failed = true; return 1;
-    }
-  if (h->fsvote) {
-    uint64_t r[8];
-    if (cmx_fxcmvote_report(h->fsvote, r)) { h->failed = true; return 1; }
-    if (r[3]) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + fxcm_vote_text(t)); h->failed = true; return 1; }
-  }
-  for (cmx_mixnet_t* m : h->sh) if (m && cmx_mixnet_sync(m)) { h->failed = true; return 1; }
-  if (h->vote) {
-    uint64_t r[8];
-    if (cmx_vote_report(h->vote, r)) { h->failed = true; return 1; }
-    if (r[3] > h->repaired_events) { unsigned long long t[8]; for (int i = 0; i < 8; ++i) t[i] = r[i]; cmx_set_err("cmx_pipeline_sync: " + vote_text(t) + repairs_text(h)); h->failed = true; return 1; }
+    if (S.vote && (kShadow[k].report(S.vote, r) || shadow_vote_check(h, k, r, -1))) { h->failed = true; return 1; }
   }
   // the multi-workgroup kernels bound every in-launch wait: one that ran out left garbage behind, not a hang
   if (cmx_lstm_failed(h->lstm)) { cmx_set_err("cmx_pipeline_sync: an in-launch hand-off of the LSTM kernels timed out (workgroups not co-resident?): the stream's output is void"); h->failed = true; return 1; }
@@ -1776,10 +1472,7 @@ int cmx_pipeline_late_start(cmx_pipeline_t* h, int last_bit) {
   if (h->compact) { cmx_set_err("cmx_pipeline_late_start: the stages share HIP streams (CMX_PIPELINE_STREAMS); a decoder needs every stage kernel running at once"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   if (hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_pipeline_late_start: device error"); return 1; }   // pretraining is complete
-  ctx_shadow_drop(h);
-  lstm_shadow_drop(h);
-  fxcm_shadow_drop(h);
-  shadow_drop(h);   // a decoder is not covered by the vote (include/cmix_amd.h): it holds no stream, workgroup or buffer of it
+  for (ShadowId k : kShadowLast) shadow_drop(h, kShadow[k]);   // a decoder is not covered by the vote (include/cmix_amd.h): it holds no stream, workgroup or buffer of it
   Late* L = new Late();
   h->late = L;
   const size_t n = kLateChunk, T = 8 * n;

@@ -75,13 +75,13 @@ def lib():
         L.cmx_fxcmvote_record.argtypes = [C.c_void_p]
         L.cmx_fxcmvote_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_fxcmvote_last.argtypes = [C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_set_fxcm_shadow.argtypes = [C.c_void_p, C.c_int]
-        L.cmx_pipeline_fxcm_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_fxcm_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_fxcm_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.cmx_pipeline_debug_fxcm_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32]
-        L.cmx_set_fxcm_shadow.argtypes = [C.c_void_p, C.c_int]
-        L.cmx_fxcm_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
+        for stem, kind in _SHADOW.items():   # the pipeline's and the engine's entry points of the four kinds of shadow stages
+            for name, args in (("pipeline_set_" + stem, [C.c_int]), ("pipeline_" + stem + "_report", [C.c_void_p]),
+                               ("pipeline_" + stem + "_values", [C.c_void_p] * kind["values_args"]),
+                               ("pipeline_" + stem + "_state_diff", [C.c_int, C.c_int, C.c_void_p]),
+                               ("pipeline_debug_" + stem + "_xor", [C.c_int, C.c_int] + [C.c_uint64] * kind["xor_words"] + [C.c_uint32]),
+                               ("set_" + stem, [C.c_int]), (stem + "_report", [C.c_void_p])):
+                getattr(L, "cmx_" + name).argtypes = [C.c_void_p] + args
         L.cmx_mixnet_create.restype = C.c_void_p
         L.cmx_mixnet_create.argtypes = [C.c_int]
         L.cmx_mixnet_destroy.argtypes = [C.c_void_p]
@@ -201,13 +201,6 @@ def lib():
         L.cmx_vote_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_mixnet_state_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_mixnet_debug_state_xor.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
-        L.cmx_pipeline_set_shadow.argtypes = [C.c_void_p, C.c_int]
-        L.cmx_pipeline_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.cmx_pipeline_debug_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]
-        L.cmx_set_shadow.argtypes = [C.c_void_p, C.c_int]
-        L.cmx_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_vote_last.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_mixnet_state_repair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_pipeline_set_shadow_repair.argtypes = [C.c_void_p, C.c_int]
@@ -231,11 +224,6 @@ def lib():
         L.cmx_ctxvote_record.argtypes = [C.c_void_p]
         L.cmx_ctxvote_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_ctxvote_last.argtypes = [C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_set_ctx_shadow.argtypes = [C.c_void_p, C.c_int]
-        L.cmx_pipeline_ctx_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_ctx_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_ctx_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.cmx_pipeline_debug_ctx_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]
         L.cmx_lstmvote_create.restype = C.c_void_p
         L.cmx_lstmvote_create.argtypes = [C.c_int, C.c_int]
         L.cmx_lstmvote_destroy.argtypes = [C.c_void_p]
@@ -248,15 +236,6 @@ def lib():
         L.cmx_lstm_state_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cmx_lstm_debug_state_xor.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32]
         L.cmx_lstm_debug_layout.argtypes = [C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_set_lstm_shadow.argtypes = [C.c_void_p, C.c_int]
-        L.cmx_pipeline_lstm_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_lstm_shadow_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cmx_pipeline_lstm_shadow_state_diff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.cmx_pipeline_debug_lstm_shadow_xor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32]
-        L.cmx_set_lstm_shadow.argtypes = [C.c_void_p, C.c_int]
-        L.cmx_lstm_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
-        L.cmx_set_ctx_shadow.argtypes = [C.c_void_p, C.c_int]
-        L.cmx_ctx_shadow_report.argtypes = [C.c_void_p, C.c_void_p]
         L.cmx_debug_ctx_shadow_xor.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]
         L.cmx_pipeline_late_start.argtypes = [C.c_void_p, C.c_int]
         L.cmx_pipeline_late_predict.restype = C.c_float
@@ -334,11 +313,16 @@ def _vote_report(fn, h):
             "odd": _opt(v[6]) if ev else None, "elements": v[7] if ev else None, "raw": v}
 
 
-def _vote_values(fn, h, n):
-    words, sel, bit = np.zeros(144, np.uint32), np.zeros(47, np.uint32), C.c_uint32(0)
-    if fn(h, words.ctypes.data, sel.ctypes.data, C.byref(bit)):
+def _values(fn, h, n, cols, scalars, sel=False):
+    """a vote's cmx_*_values as a dict: words [n, cols] u32 (the capture of the first event), sel [47] u32 where the vote has selectors, then its scalars"""
+    words, sel, out = np.zeros(3 * cols, np.uint32), [np.zeros(47, np.uint32)] if sel else [], [C.c_uint32(0) for _ in scalars]
+    if fn(h, words.ctypes.data, *[a.ctypes.data for a in sel], *[C.byref(x) for x in out]):
         raise CmxError(last_error())
-    return {"words": words[:48 * n].reshape(n, 48).copy(), "sel": sel, "bit": int(bit.value)}
+    return {"words": words[:cols * n].reshape(n, cols).copy(), **({"sel": sel[0]} if sel else {}), **{k: int(x.value) for k, x in zip(scalars, out)}}
+
+
+def _vote_values(fn, h, n):
+    return _values(fn, h, n, 48, ("bit",), sel=True)
 
 
 def _state_diff(out):
@@ -448,10 +432,7 @@ CTX_COMPACT_STRIDE = 64
 
 
 def _ctx_vote_values(fn, h, n):
-    words, bit = np.zeros(3 * CTXVOTE_COLS, np.uint32), C.c_uint32(0)
-    if fn(h, words.ctypes.data, C.byref(bit)):
-        raise CmxError(last_error())
-    return {"words": words[:CTXVOTE_COLS * n].reshape(n, CTXVOTE_COLS).copy(), "bit": int(bit.value)}
+    return _values(fn, h, n, CTXVOTE_COLS, ("bit",))
 
 
 def _ctx_state_diff(out):
@@ -507,16 +488,14 @@ LSTM_STATE_ARRAYS = tuple(["%s[%d][%d]" % (a, l, g) for a in ("W", "WT", "M", "V
 
 
 def _lstm_vote_values(fn, h, n):
-    words, byte = np.zeros(3 * LSTMVOTE_COLS, np.uint32), C.c_uint32(0)
-    if fn(h, words.ctypes.data, C.byref(byte)):
-        raise CmxError(last_error())
-    return {"words": words[:LSTMVOTE_COLS * n].reshape(n, LSTMVOTE_COLS).copy(), "byte": int(byte.value)}
+    return _values(fn, h, n, LSTMVOTE_COLS, ("byte",))
 
 
-def _lstm_state_diff(out):
+def _lstm_state_diff(out, regions=LSTM_STATE_REGIONS):
+    """cmx_lstm_state_diff's words, and cmx_fxcm_state_diff's with its regions"""
     v = [int(x) for x in out]
     first = {"region": v[1], "index": v[2], "a": v[3], "b": v[4]} if v[0] else None
-    return {"words": v[0], "first": first, "per_region": dict(zip(LSTM_STATE_REGIONS, v[5:16])), "raw": v}
+    return {"words": v[0], "first": first, "per_region": dict(zip(regions, v[5:5 + len(regions)])), "raw": v}
 
 
 def lstm_layout(lstm):
@@ -576,16 +555,11 @@ FXCM_STATE_ARRAYS = tuple(["squash", "stretch", "wrt"] + ["sta[%d]" % i for i in
 
 
 def _fxcm_vote_values(fn, h, n):
-    words, bit, byte = np.zeros(3 * FXCMVOTE_COLS, np.uint32), C.c_uint32(0), C.c_uint32(0)
-    if fn(h, words.ctypes.data, C.byref(bit), C.byref(byte)):
-        raise CmxError(last_error())
-    return {"words": words[:FXCMVOTE_COLS * n].reshape(n, FXCMVOTE_COLS).copy(), "bit": int(bit.value), "byte": int(byte.value)}
+    return _values(fn, h, n, FXCMVOTE_COLS, ("bit", "byte"))
 
 
 def _fxcm_state_diff(out):
-    v = [int(x) for x in out]
-    first = {"region": v[1], "index": v[2], "a": v[3], "b": v[4]} if v[0] else None
-    return {"words": v[0], "first": first, "per_region": dict(zip(FXCM_STATE_REGIONS, v[5:17])), "raw": v}
+    return _lstm_state_diff(out, FXCM_STATE_REGIONS)
 
 
 def fxcm_layout(fx):
@@ -1059,8 +1033,49 @@ def bytemodel_bits(dist0, dist_rest, data, layer0, col, device=0, stream=None):
         raise CmxError(last_error())
 
 
-class Pipeline:
+# The four kinds of shadow stages (include/cmix_amd.h, cmx_pipeline_set_shadow and its three kin) by the stem of their C symbols: how a vote's captured
+# values decode and how many pointers the call takes, how a state_diff decodes and its words, the state regions' names, and the u64 words that
+# debug_*_xor takes between the region and the mask
+_SHADOW = {
+    "shadow": {"values": _vote_values, "values_args": 3, "diff": _state_diff, "diff_len": 20, "regions": STATE_REGIONS, "xor_words": 3},
+    "ctx_shadow": {"values": _ctx_vote_values, "values_args": 2, "diff": _ctx_state_diff, "diff_len": 16, "regions": CTX_STATE_REGIONS, "xor_words": 2},
+    "lstm_shadow": {"values": _lstm_vote_values, "values_args": 2, "diff": _lstm_state_diff, "diff_len": 16, "regions": LSTM_STATE_REGIONS, "xor_words": 1},
+    "fxcm_shadow": {"values": _fxcm_vote_values, "values_args": 3, "diff": _fxcm_state_diff, "diff_len": 17, "regions": FXCM_STATE_REGIONS, "xor_words": 1},
+}
+
+
+class _Shadows:
+    """The calls behind Pipeline's and Predictor's shadow methods, by kind (a key of _SHADOW); _C is the front of the class's C symbols."""
+
+    def _shadow_c(self, name):
+        return getattr(lib(), self._C + name)
+
+    def _shadow_set(self, stem, k):
+        if self._shadow_c("set_" + stem)(self.h, int(k)):
+            raise CmxError(last_error())
+        setattr(self, "_" + stem, int(k))
+
+    def _shadow_report(self, stem):
+        return _vote_report(self._shadow_c(stem + "_report"), self.h)
+
+    def _shadow_values(self, stem):
+        return _SHADOW[stem]["values"](self._shadow_c(stem + "_values"), self.h, 1 + getattr(self, "_" + stem, 0))
+
+    def _shadow_state_diff(self, stem, a, b):
+        out = (C.c_uint64 * _SHADOW[stem]["diff_len"])()
+        if self._shadow_c(stem + "_state_diff")(self.h, int(a), int(b), out):
+            raise CmxError(last_error())
+        return _SHADOW[stem]["diff"](out)
+
+    def _shadow_xor(self, stem, head, region, where, xor_mask):
+        """head: (instance,), or a Predictor's (after_chunk, instance); where: the kind's words between region and mask"""
+        if self._shadow_c("debug_" + stem + "_xor")(self.h, *[int(x) for x in head], _region(region, _SHADOW[stem]["regions"]), *where, int(xor_mask)):
+            raise CmxError(last_error())
+
+
+class Pipeline(_Shadows):
     """One stream through every stage built so far (native orchestration in libcmixamd.so)."""
+    _C = "cmx_pipeline_"
 
     def __init__(self, vocab, device=0, max_chunk_bytes=4096):
         vocab = np.ascontiguousarray(vocab, np.uint8)
@@ -1190,9 +1205,7 @@ class Pipeline:
     def set_shadow(self, k):
         """k = 0 / 1 / 2 shadow mixing networks voting on every chunk (include/cmix_amd.h): before the first chunk; wait / fetch / sync then fail
         the chunk in which the instances disagree."""
-        if lib().cmx_pipeline_set_shadow(self.h, int(k)):
-            raise CmxError(last_error())
-        self._shadow = int(k)
+        self._shadow_set("shadow", k)
 
     def set_journal(self, log2=19):
         """The stream journal (include/cmix_amd.h, cmx_pipeline_set_journal): blocks of 2^log2 bits, 0 = off; before the first chunk."""
@@ -1226,104 +1239,82 @@ class Pipeline:
 
     def shadow_report(self):
         """as Vote.report (all zero while nothing was voted)"""
-        return _vote_report(lib().cmx_pipeline_shadow_report, self.h)
+        return self._shadow_report("shadow")
 
     def shadow_values(self):
         """as Vote.values"""
-        return _vote_values(lib().cmx_pipeline_shadow_values, self.h, 1 + getattr(self, "_shadow", 0))
+        return self._shadow_values("shadow")
 
     def shadow_state_diff(self, a, b):
         """MixNet.state_diff of instances a and b (0 = the stream's own network, 1.. = the shadows)"""
-        out = (C.c_uint64 * 20)()
-        if lib().cmx_pipeline_shadow_state_diff(self.h, int(a), int(b), out):
-            raise CmxError(last_error())
-        return _state_diff(out)
+        return self._shadow_state_diff("shadow", a, b)
 
     def debug_shadow_xor(self, instance, region, mixer, row, index, xor_mask):
         """Test hook: MixNet.debug_state_xor on one instance, between chunks."""
-        if lib().cmx_pipeline_debug_shadow_xor(self.h, int(instance), _region(region), _u64(mixer), _u64(row), _u64(index), int(xor_mask)):
-            raise CmxError(last_error())
+        self._shadow_xor("shadow", (instance,), region, (_u64(mixer), _u64(row), _u64(index)), xor_mask)
 
     def set_ctx_shadow(self, k):
         """k = 0 / 1 / 2 shadow context stages voting on every chunk's 54 columns and 47 selectors (include/cmix_amd.h): before the first chunk and
         before pretrain; wait / fetch / sync then fail the chunk in which the instances disagree."""
-        if lib().cmx_pipeline_set_ctx_shadow(self.h, int(k)):
-            raise CmxError(last_error())
-        self._ctx_shadow = int(k)
+        self._shadow_set("ctx_shadow", k)
 
     def ctx_shadow_report(self):
         """as CtxVote.report (all zero while nothing was voted)"""
-        return _vote_report(lib().cmx_pipeline_ctx_shadow_report, self.h)
+        return self._shadow_report("ctx_shadow")
 
     def ctx_shadow_values(self):
         """as CtxVote.values"""
-        return _ctx_vote_values(lib().cmx_pipeline_ctx_shadow_values, self.h, 1 + getattr(self, "_ctx_shadow", 0))
+        return self._shadow_values("ctx_shadow")
 
     def ctx_shadow_state_diff(self, a, b):
         """CtxModels.state_diff of instances a and b (0 = the stream's own stage, 1.. = the shadows)"""
-        out = (C.c_uint64 * 16)()
-        if lib().cmx_pipeline_ctx_shadow_state_diff(self.h, int(a), int(b), out):
-            raise CmxError(last_error())
-        return _ctx_state_diff(out)
+        return self._shadow_state_diff("ctx_shadow", a, b)
 
     def debug_ctx_shadow_xor(self, instance, region, lane, index, xor_mask):
         """Test hook: CtxModels.debug_state_xor on one instance, between chunks."""
-        if lib().cmx_pipeline_debug_ctx_shadow_xor(self.h, int(instance), _region(region, CTX_STATE_REGIONS), _u64(lane), int(index), int(xor_mask)):
-            raise CmxError(last_error())
+        self._shadow_xor("ctx_shadow", (instance,), region, (_u64(lane), int(index)), xor_mask)
 
     def set_lstm_shadow(self, k):
         """k = 0 / 1 / 2 shadow LSTM stages voting on every chunk's distributions, bit predictions and ex (include/cmix_amd.h): before the first
         chunk (pretrain may have run: the LSTM is not pretrained); wait / fetch / sync then fail the chunk in which the instances disagree."""
-        if lib().cmx_pipeline_set_lstm_shadow(self.h, int(k)):
-            raise CmxError(last_error())
-        self._lstm_shadow = int(k)
+        self._shadow_set("lstm_shadow", k)
 
     def lstm_shadow_report(self):
         """as LstmVote.report (all zero while nothing was voted)"""
-        return _vote_report(lib().cmx_pipeline_lstm_shadow_report, self.h)
+        return self._shadow_report("lstm_shadow")
 
     def lstm_shadow_values(self):
         """as LstmVote.values"""
-        return _lstm_vote_values(lib().cmx_pipeline_lstm_shadow_values, self.h, 1 + getattr(self, "_lstm_shadow", 0))
+        return self._shadow_values("lstm_shadow")
 
     def lstm_shadow_state_diff(self, a, b):
         """Lstm.state_diff of instances a and b (0 = the stream's own stage, 1.. = the shadows)"""
-        out = (C.c_uint64 * 16)()
-        if lib().cmx_pipeline_lstm_shadow_state_diff(self.h, int(a), int(b), out):
-            raise CmxError(last_error())
-        return _lstm_state_diff(out)
+        return self._shadow_state_diff("lstm_shadow", a, b)
 
     def debug_lstm_shadow_xor(self, instance, region, index, xor_mask):
         """Test hook: Lstm.debug_state_xor on one instance, between chunks."""
-        if lib().cmx_pipeline_debug_lstm_shadow_xor(self.h, int(instance), _region(region, LSTM_STATE_REGIONS), int(index), int(xor_mask)):
-            raise CmxError(last_error())
+        self._shadow_xor("lstm_shadow", (instance,), region, (int(index),), xor_mask)
 
     def set_fxcm_shadow(self, k):
         """k = 0 / 1 / 2 shadow fxcm stages voting on every chunk's 431 columns (include/cmix_amd.h): after enable_fxcm, before the first chunk and
         before pretrain (fxcm learns the dictionary); wait / fetch / sync then fail the chunk in which the instances disagree."""
-        if lib().cmx_pipeline_set_fxcm_shadow(self.h, int(k)):
-            raise CmxError(last_error())
-        self._fxcm_shadow = int(k)
+        self._shadow_set("fxcm_shadow", k)
 
     def fxcm_shadow_report(self):
         """as FxcmVote.report (all zero while nothing was voted)"""
-        return _vote_report(lib().cmx_pipeline_fxcm_shadow_report, self.h)
+        return self._shadow_report("fxcm_shadow")
 
     def fxcm_shadow_values(self):
         """as FxcmVote.values"""
-        return _fxcm_vote_values(lib().cmx_pipeline_fxcm_shadow_values, self.h, 1 + getattr(self, "_fxcm_shadow", 0))
+        return self._shadow_values("fxcm_shadow")
 
     def fxcm_shadow_state_diff(self, a, b):
         """Fxcm.state_diff of instances a and b (0 = the stream's own stage, 1.. = the shadows), between chunks"""
-        out = (C.c_uint64 * 17)()
-        if lib().cmx_pipeline_fxcm_shadow_state_diff(self.h, int(a), int(b), out):
-            raise CmxError(last_error())
-        return _fxcm_state_diff(out)
+        return self._shadow_state_diff("fxcm_shadow", a, b)
 
     def debug_fxcm_shadow_xor(self, instance, region, index, xor_mask):
         """Test hook: Fxcm.debug_state_xor on one instance, between chunks."""
-        if lib().cmx_pipeline_debug_fxcm_shadow_xor(self.h, int(instance), _region(region, FXCM_STATE_REGIONS), int(index), int(xor_mask)):
-            raise CmxError(last_error())
+        self._shadow_xor("fxcm_shadow", (instance,), region, (int(index),), xor_mask)
 
     def mixnet_mode(self):
         """0 strict (bit-exact, the default), 1 tolerance -- as the library reports it"""
@@ -1522,12 +1513,13 @@ def header_read(buf):
     return length.value, bool(dic.value), vocab, n
 
 
-class Predictor:
+class Predictor(_Shadows):
     """`class Predictor` (src/predictor.h:17-22) over cmx_create .. cmx_destroy: Predict / Perceive / Pretrain in the
     reference's strict per-bit protocol. Two modes, decided by the first call that needs device state: after
     `stage_input` (a compressor knows its bytes) the handle runs the chunk pipeline with every model family on the device and
     Predict / Perceive pop and check; without it the per-bit stages are built (what a Decoder needs) and the fxcm / paq8
     columns of each bit come from the caller (`set_model_outputs`)."""
+    _C = "cmx_"
 
     def __init__(self, vocab, device=0, dict_path=None):
         vocab = np.ascontiguousarray(vocab, np.uint8)
@@ -1580,8 +1572,7 @@ class Predictor:
 
     def set_shadow(self, k):
         """Shadow mixing networks of the look-ahead pipeline (include/cmix_amd.h, cmx_set_shadow): before the first stage_input / Predict."""
-        if lib().cmx_set_shadow(self.h, int(k)):
-            raise CmxError(last_error())
+        self._shadow_set("shadow", k)
 
     def set_shadow_repair(self, max_repairs):
         """Repair on the majority (include/cmix_amd.h, cmx_set_shadow_repair): after set_shadow(2), before the first stage_input / Predict."""
@@ -1594,40 +1585,35 @@ class Predictor:
 
     def debug_shadow_xor(self, after_chunk, instance, region, mixer, row, index, xor_mask):
         """Test hook: one Pipeline.debug_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""
-        if lib().cmx_debug_shadow_xor(self.h, int(after_chunk), int(instance), _region(region), _u64(mixer), _u64(row), _u64(index), int(xor_mask)):
-            raise CmxError(last_error())
+        self._shadow_xor("shadow", (after_chunk, instance), region, (_u64(mixer), _u64(row), _u64(index)), xor_mask)
 
     def set_ctx_shadow(self, k):
         """Shadow context stages of the look-ahead pipeline (include/cmix_amd.h, cmx_set_ctx_shadow): before the first stage_input / Predict."""
-        if lib().cmx_set_ctx_shadow(self.h, int(k)):
-            raise CmxError(last_error())
+        self._shadow_set("ctx_shadow", k)
 
     def ctx_shadow_report(self):
         """as CtxVote.report (all zero unless the handle compresses)"""
-        return _vote_report(lib().cmx_ctx_shadow_report, self.h)
+        return self._shadow_report("ctx_shadow")
 
     def set_lstm_shadow(self, k):
         """Shadow LSTM stages of the look-ahead pipeline (include/cmix_amd.h, cmx_set_lstm_shadow): before the first stage_input / Predict."""
-        if lib().cmx_set_lstm_shadow(self.h, int(k)):
-            raise CmxError(last_error())
+        self._shadow_set("lstm_shadow", k)
 
     def lstm_shadow_report(self):
         """as LstmVote.report (all zero unless the handle compresses)"""
-        return _vote_report(lib().cmx_lstm_shadow_report, self.h)
+        return self._shadow_report("lstm_shadow")
 
     def set_fxcm_shadow(self, k):
         """Shadow fxcm stages of the look-ahead pipeline (include/cmix_amd.h, cmx_set_fxcm_shadow): before the first stage_input / Predict."""
-        if lib().cmx_set_fxcm_shadow(self.h, int(k)):
-            raise CmxError(last_error())
+        self._shadow_set("fxcm_shadow", k)
 
     def fxcm_shadow_report(self):
         """as FxcmVote.report (all zero unless the handle compresses)"""
-        return _vote_report(lib().cmx_fxcm_shadow_report, self.h)
+        return self._shadow_report("fxcm_shadow")
 
     def debug_ctx_shadow_xor(self, after_chunk, instance, region, lane, index, xor_mask):
         """Test hook: one Pipeline.debug_ctx_shadow_xor between look-ahead chunk `after_chunk` and the next (include/cmix_amd.h)."""
-        if lib().cmx_debug_ctx_shadow_xor(self.h, int(after_chunk), int(instance), _region(region, CTX_STATE_REGIONS), _u64(lane), int(index), int(xor_mask)):
-            raise CmxError(last_error())
+        self._shadow_xor("ctx_shadow", (after_chunk, instance), region, (_u64(lane), int(index)), xor_mask)
 
     def set_journal(self, log2=19):
         """The stream journal (include/cmix_amd.h, cmx_set_journal): a compressor's handle journals every chunk on the device, a decoder's folds the p
@@ -1650,7 +1636,7 @@ class Predictor:
 
     def shadow_report(self):
         """as Vote.report (all zero unless the handle compresses)"""
-        return _vote_report(lib().cmx_shadow_report, self.h)
+        return self._shadow_report("shadow")
 
     def decode_stream(self, code, nbytes):
         """Decoder::Decode over a whole stream inside the library (cmx_decode_stream): the arithmetic code behind the container header -> the nbytes
