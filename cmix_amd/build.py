@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "lib", "libcmixamd.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["cmx_api.hip", "mixnet_kernels.hip", "mixnet_chunk.hip", "mixnet_vote.hip", "lstm_api.hip", "lstm_kernels.hip", "lstm_block.hip", "lstm_vote.hip",
            "ctxmodels_api.hip", "ctxmodels_kernels.hip", "ctxmodels_vote.hip", "ppmd_host.cpp", "pipeline_api.hip", "coder_host.cpp", "engine_api.hip",
-           "fxcm_stage.hip", "fxcm_vote.hip", "fxcm_parser_host.cpp", "p8stage.hip", "journal.hip", "journal_host.cpp"]
+           "fxcm_stage.hip", "fxcm_vote.hip", "fxcm_parser_host.cpp", "p8stage.hip", "journal.hip", "journal_host.cpp", "state_digest.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value"]
 # the paq8 stage's host front end: plain C (gcc), every allocation tracked through the force-included p8f_alloc.h
 FRONT_DIR = os.path.join(CSRC, "p8front")

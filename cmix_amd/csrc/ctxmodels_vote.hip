@@ -21,6 +21,7 @@
 
 #include "../../include/cmix_amd.h"
 #include "cmx_vote_core.h"
+#include "cmx_state_digest.h"
 #include "ctxmodels_state.h"
 
 extern "C" int cmx_ctxmodels_state_view(cmx_ctxmodels_t* h, const CtxRegion** regions, int* n, int* device);   // ctxmodels_api.hip
@@ -142,6 +143,16 @@ int cmx_ctxmodels_state_diff(cmx_ctxmodels_t* a, cmx_ctxmodels_t* b, uint64_t ou
   if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_ctxmodels_state_diff: device error"); return 1; }
   return 0;
 }
+
+// one column per array of the state view (region-then-lane order); the stage compares nothing on the host
+static int ctx_digest(const char* who, cmx_ctxmodels_t* h, uint64_t* out, size_t cap, int layout) {
+  if (!h) { cmx_set_err(std::string(who) + ": null handle"); return -1; }
+  std::vector<StateArray> rg; int dev = 0;
+  if (ctx_arrays(h, rg, &dev)) return -1;
+  return cmx_state_digest_stage(who, dev, rg.data(), (int)rg.size(), nullptr, 0, out, cap, layout);
+}
+int cmx_ctxmodels_state_digest(cmx_ctxmodels_t* h, uint64_t* out, size_t cap) { return ctx_digest("cmx_ctxmodels_state_digest", h, out, cap, 0); }
+int cmx_ctxmodels_state_digest_layout(cmx_ctxmodels_t* h, uint64_t* out, size_t cap) { return ctx_digest("cmx_ctxmodels_state_digest_layout", h, out, cap, 1); }
 
 int cmx_ctxmodels_debug_state_xor(cmx_ctxmodels_t* h, int region, uint64_t lane, uint64_t index, uint32_t xor_mask) {
   if (!h) { cmx_set_err("cmx_ctxmodels_debug_state_xor: null handle"); return 1; }

@@ -102,6 +102,10 @@ struct cmx_engine {
   bool jr_env = false;            // the path came from CMIX_JOURNAL (cmx_create): cmx_perceive writes the completed blocks every MiB, cmx_destroy closes the files
   bool jr_closed = false;         // cmx_journal_close_files ran
   uint64_t jr_bits = 0;           // bits perceived since cmx_create (the MiB marks)
+  int state_journal = 0;          // cmx_set_state_journal: the look-ahead pipeline takes a record of every stage's state digests after every that-many-th chunk (0 = off)
+  std::string sj_path;            // ... and appends it to this file (cmx_state_journal_write_file, or CMIX_STATE_JOURNAL read by cmx_create)
+  bool sj_env = false;            // the switch came from the environment: a decoder says that it is not covered and carries on
+  bool sj_closed = false;         // cmx_state_journal_close ran
   int mode = 0;                   // 0 undecided, 1 per-bit stages built (columns from the caller), 2 look-ahead pipeline built, 3 the decoder's pipeline (late-bit protocol)
   LookAhead* la = nullptr;
   cmx_pipeline_t* late = nullptr; // mode 3: every model family on the device, bits arriving one at a time (cmx_pipeline_late_*)
@@ -291,6 +295,11 @@ int ensure_late(cmx_engine* h, const char* where) {
   if (h->mode == 3) return 0;
   if (h->mode != 0) { cmx_set_err(std::string(where) + ": the handle is already in another mode"); return 1; }
   if (h->pre_j) { cmx_set_err(std::string(where) + ": Pretrain() stopped inside a byte"); return 1; }
+  if (h->state_journal) {   // (the pipeline's late_start would refuse it)
+    if (!h->sj_env) { cmx_set_err(std::string(where) + ": the state journal is on (cmx_set_state_journal); it does not cover a decoder, whose kernels are resident and whose stream has no rest point"); return 1; }
+    fprintf(stderr, "cmix_amd: CMIX_STATE_JOURNAL: the state journal does not cover a decoder (its kernels are resident, the stream has no rest point); decoding without it\n");
+    h->state_journal = 0;
+  }
   double t0 = cmx_timing_now();
   if (cmx_timing_on()) fprintf(stderr, "[cmx timing] first predict (decoder) at    %.3f s (process clock)\n", t0);
   h->late = cmx_pipeline_create(h->vocab, h->device, kLaChunk);
@@ -348,6 +357,8 @@ int ensure_lookahead(cmx_engine* h) {
     if (k == SH_MIX) ok = ok && (!h->shadow_repair || cmx_pipeline_set_shadow_repair(la->pipe, h->shadow_repair) == 0);
   }
   ok = ok && (!h->journal || cmx_pipeline_set_journal(la->pipe, h->journal) == 0);
+  ok = ok && (!h->state_journal || cmx_pipeline_set_state_journal(la->pipe, h->state_journal) == 0);
+  ok = ok && (!h->state_journal || h->sj_path.empty() || cmx_pipeline_state_journal_write_file(la->pipe, h->sj_path.c_str(), 0) == 0);   // (the header lines now, every record as it is taken)
   if (ok && h->jr_check) { cmx_set_err("cmx_stage_input: a journal to check against is set (cmx_set_journal_check), which covers a decoder only"); ok = false; }
   if (!ok) { free_lookahead(h); return 1; }   // the failing stage has set the error
   const size_t T = 8 * kLaChunk;
@@ -450,6 +461,14 @@ static int journal_from_env(cmx_engine* h) {
   else if (jr && jr[0] && cmx_set_journal(h, jl ? atoi(jl) : 19)) return 1;
   if (jr && jr[0]) { h->jr_path = jr; h->jr_written = 0; }
   h->jr_env = (jr && jr[0]) || (jc && jc[0]);
+  // CMIX_STATE_JOURNAL=path [CMIX_STATE_JOURNAL_EVERY=n chunks, default CMX_STATE_JOURNAL_EVERY]: the state journal, read here for the same reason
+  const char* sj = getenv("CMIX_STATE_JOURNAL");
+  const char* se = getenv("CMIX_STATE_JOURNAL_EVERY");
+  if (sj && sj[0]) {
+    const int every = se && se[0] ? atoi(se) : CMX_STATE_JOURNAL_EVERY;
+    if (every <= 0) { cmx_set_err("cmx_create: CMIX_STATE_JOURNAL_EVERY must be a number of chunks (1 or more)"); return 1; }
+    h->state_journal = every; h->sj_path = sj; h->sj_env = true;
+  }
   return 0;
 }
 // every MiB of a journal switched on by CMIX_JOURNAL: the blocks completed so far go to the files, so a run that is killed leaves them behind
@@ -463,6 +482,7 @@ void cmx_destroy(cmx_t* h) {
   (void)hipSetDevice(h->device);
   // a journal switched on by the environment that the program did not close itself: the rest of it, and a checked decode's last block (nothing can be returned here)
   if (h->jr_env && !h->jr_closed && !h->failed && cmx_journal_close_files(h)) fprintf(stderr, "cmix_amd: %s\n", cmx_last_error());
+  if (h->state_journal && !h->sj_closed && !h->failed && cmx_state_journal_close(h)) fprintf(stderr, "cmix_amd: %s\n", cmx_last_error());   // the record after the last chunk
   if (h->late) (void)cmx_pipeline_late_stop(h->late);   // FIRST: a decoder's stage kernels wait for bits that will not come -- without the abort word a
                                                         // device-wide synchronisation waits for their wall-clock time-outs (30 s per chunk in flight)
   (void)hipDeviceSynchronize();
@@ -828,6 +848,28 @@ int cmx_journal_close_files(cmx_t* h) {
   std::string err;
   if (h->hj && cmx_hostjournal_check_tail(h->hj, &err)) { cmx_set_err("cmx_journal_close_files: " + err); return 1; }
   return 0;
+}
+
+// ---- the state journal of a cmx_t (include/cmix_amd.h): a look-ahead compressor's pipeline takes and writes the records ----
+int cmx_set_state_journal(cmx_t* h, int every_chunks) {
+  if (!h) { cmx_set_err("cmx_set_state_journal: null handle"); return 1; }
+  if (every_chunks < 0) { cmx_set_err("cmx_set_state_journal: every_chunks must be 0 (off) or a number of chunks"); return 1; }
+  if (h->mode != 0 || h->started) { cmx_set_err("cmx_set_state_journal: only before the first cmx_stage_input / cmx_predict"); return 1; }
+  h->state_journal = every_chunks; h->sj_env = false;
+  return 0;
+}
+int cmx_state_journal_write_file(cmx_t* h, const char* path) {
+  if (!h || !path || !path[0]) { cmx_set_err("cmx_state_journal_write_file: bad argument"); return 1; }
+  if (!h->state_journal) { cmx_set_err("cmx_state_journal_write_file: the state journal is off (cmx_set_state_journal)"); return 1; }
+  if (!h->sj_path.empty() && h->sj_path != path) { cmx_set_err("cmx_state_journal_write_file: this handle's state journal is being written to " + h->sj_path); return 1; }
+  h->sj_path = path;
+  return h->mode == 2 && h->la ? cmx_pipeline_state_journal_write_file(h->la->pipe, path, 0) : 0;   // (else: when the pipeline is built)
+}
+int cmx_state_journal_close(cmx_t* h) {
+  if (!h) { cmx_set_err("cmx_state_journal_close: null handle"); return 1; }
+  if (!h->state_journal || h->sj_path.empty() || h->mode != 2 || !h->la) return 0;   // (nothing to close, so a program may call this whatever its environment says)
+  h->sj_closed = true;
+  return cmx_pipeline_state_journal_write_file(h->la->pipe, h->sj_path.c_str(), 1);
 }
 
 // 0 undecided, 1 per-bit stages, 2 look-ahead pipeline; in mode 2 *chunks_in_flight (may be NULL) = submitted - used up

@@ -26,6 +26,7 @@
 
 #include "../../include/cmix_amd.h"
 #include "cmx_vote_core.h"
+#include "cmx_state_digest.h"
 #include "fxcm_rec.h"
 #include "fxcm_state.h"
 
@@ -203,6 +204,20 @@ int cmx_fxcm_state_diff(cmx_fxcm_t* a, cmx_fxcm_t* b, uint64_t out[CMX_FXCM_STAT
     }
   return 0;
 }
+
+// one column per array of the state view, then region 11: FxDev with its device pointers zeroed, and behind it the host-side counter bytes_done
+static int fx_digest(const char* who, cmx_fxcm_t* h, uint64_t* out, size_t cap, int layout) {
+  if (!h) { cmx_set_err(std::string(who) + ": null handle"); return -1; }
+  std::vector<StateArray> rg; int dev = 0;
+  uint64_t done = 0;
+  if (fx_arrays(h, rg, &dev, &done)) return -1;
+  std::vector<uint32_t> w;
+  if (cmx_fxcm_dev_words(h, w)) return -1;
+  w.push_back((uint32_t)done); w.push_back((uint32_t)(done >> 32));
+  return cmx_state_digest_stage(who, dev, rg.data(), (int)rg.size(), &w, FX_REGION_DEV, out, cap, layout);
+}
+int cmx_fxcm_state_digest(cmx_fxcm_t* h, uint64_t* out, size_t cap) { return fx_digest("cmx_fxcm_state_digest", h, out, cap, 0); }
+int cmx_fxcm_state_digest_layout(cmx_fxcm_t* h, uint64_t* out, size_t cap) { return fx_digest("cmx_fxcm_state_digest_layout", h, out, cap, 1); }
 
 int cmx_fxcm_debug_state_xor(cmx_fxcm_t* h, int region, uint64_t index, uint32_t xor_mask) {
   if (!h) { cmx_set_err("cmx_fxcm_debug_state_xor: null handle"); return 1; }

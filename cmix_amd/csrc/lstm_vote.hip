@@ -24,6 +24,7 @@
 
 #include "../../include/cmix_amd.h"
 #include "cmx_vote_core.h"
+#include "cmx_state_digest.h"
 #include "lstm_state.h"
 
 extern "C" int cmx_lstm_state_view(cmx_lstm_t* h, LstmRegion* out, int* n, int* device, uint64_t counters[3]);   // lstm_api.hip
@@ -151,6 +152,19 @@ int cmx_lstm_state_diff(cmx_lstm_t* a, cmx_lstm_t* b, uint64_t out[16]) {
   if (!ok) { (void)hipGetLastError(); cmx_set_err("cmx_lstm_state_diff: device error"); return 1; }
   return 0;
 }
+
+// one column per array of the state view, then the three host-side counters (bytes_done, hc, bptt_rounds; two words each) as region 11
+static int lstm_digest(const char* who, cmx_lstm_t* h, uint64_t* out, size_t cap, int layout) {
+  if (!h) { cmx_set_err(std::string(who) + ": null handle"); return -1; }
+  std::vector<StateArray> rg; int dev = 0;
+  uint64_t c[3] = {0, 0, 0};
+  if (lstm_arrays(h, rg, &dev, c)) return -1;
+  std::vector<uint32_t> w(6);
+  memcpy(w.data(), c, sizeof c);
+  return cmx_state_digest_stage(who, dev, rg.data(), (int)rg.size(), &w, CMX_LSTM_STATE_REGIONS, out, cap, layout);
+}
+int cmx_lstm_state_digest(cmx_lstm_t* h, uint64_t* out, size_t cap) { return lstm_digest("cmx_lstm_state_digest", h, out, cap, 0); }
+int cmx_lstm_state_digest_layout(cmx_lstm_t* h, uint64_t* out, size_t cap) { return lstm_digest("cmx_lstm_state_digest_layout", h, out, cap, 1); }
 
 int cmx_lstm_debug_state_xor(cmx_lstm_t* h, int region, uint64_t index, uint32_t xor_mask) {
   if (!h) { cmx_set_err("cmx_lstm_debug_state_xor: null handle"); return 1; }

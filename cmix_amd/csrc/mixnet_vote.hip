@@ -20,9 +20,11 @@
 #include <stdint.h>
 #include <string.h>
 #include <string>
+#include <vector>
 
 #include "../../include/cmix_amd.h"
 #include "cmx_vote_core.h"
+#include "cmx_state_digest.h"
 #include "mixnet_state.h"
 #include "cmx_verify.h"
 
@@ -313,6 +315,28 @@ static int state_walk(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20], bool r
 }
 int cmx_mixnet_state_diff(cmx_mixnet_t* a, cmx_mixnet_t* b, uint64_t out[20]) { return state_walk(a, b, out, false); }
 int cmx_mixnet_state_repair(cmx_mixnet_t* dst, cmx_mixnet_t* src, uint64_t out[20]) { return state_walk(dst, src, out, true); }
+
+// the ten arrays of regions_of, then region 10: the scalar words
+static int mix_digest(const char* who, cmx_mixnet_t* net, uint64_t* out, size_t cap, int layout) {
+  if (!net) { cmx_set_err(std::string(who) + ": null handle"); return -1; }
+  const MixState* hs = nullptr; MixState* ds = nullptr; int dev = 0;
+  if (cmx_mixnet_state_view(net, &hs, &ds, &dev)) return -1;
+  Region r[10];
+  regions_of(*hs, r);
+  StateArray a[10];
+  for (int i = 0; i < 10; ++i) a[i] = {(uint32_t*)r[i].p, r[i].words, i, -1};
+  std::vector<uint32_t> w(kScalarWords);
+  if (out && !layout) {
+    MixState s;
+    if (hipSetDevice(dev) != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(&s, ds, sizeof s, hipMemcpyDeviceToHost) != hipSuccess) {
+      (void)hipGetLastError(); cmx_set_err(std::string(who) + ": device error"); return -1;
+    }
+    scalar_words(s, w.data());
+  }
+  return cmx_state_digest_stage(who, dev, a, 10, &w, 10, out, cap, layout);
+}
+int cmx_mixnet_state_digest(cmx_mixnet_t* net, uint64_t* out, size_t cap) { return mix_digest("cmx_mixnet_state_digest", net, out, cap, 0); }
+int cmx_mixnet_state_digest_layout(cmx_mixnet_t* net, uint64_t* out, size_t cap) { return mix_digest("cmx_mixnet_state_digest_layout", net, out, cap, 1); }
 
 int cmx_mixnet_debug_state_xor(cmx_mixnet_t* net, int region, uint64_t mixer, uint64_t row, uint64_t index, uint32_t xor_mask) {
   if (!net) { cmx_set_err("cmx_mixnet_debug_state_xor: null handle"); return 1; }

@@ -32,6 +32,7 @@
 #include "p8stage_build.h"
 #include "cmx_late.h"
 #include "cmx_streams.h"
+#include "cmx_state_digest.h"
 
 void cmx_set_err(const std::string& s);  // cmx_api.hip
 extern "C" int cmx_device_count(void);
@@ -1224,11 +1225,12 @@ __global__ __launch_bounds__(XMX_THREADS) void cmx_p8s_xmix_kernel(const P8MixDe
 namespace {
 struct DevPolicy {
   std::vector<void*> blocks;
+  std::vector<size_t> sizes;   // bytes asked for, block by block (cmx_p8stage_state_view)
   bool ok = true;
   void* zalloc(size_t bytes) {
     void* p = nullptr;
     if (!ok || hipMalloc(&p, bytes + 64) != hipSuccess || hipMemset(p, 0, bytes + 64) != hipSuccess) { ok = false; return nullptr; }
-    blocks.push_back(p);
+    blocks.push_back(p); sizes.push_back(bytes);
     return p;
   }
   void upload(void* dst, const void* src, size_t bytes) { if (dst && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) ok = false; }
@@ -1261,6 +1263,7 @@ struct cmx_p8stage {
   P8TailDev* d_tail = nullptr; P8MixDev* d_mix = nullptr;
   P8CmDev* d_xfam[P8_NMODEL - 1] = {}; P8XLanesDev* d_xlanes[P8_NMODEL - 1] = {};   // the image models (p8_rec.h P8XLayout)
   P8ViewMap xview[P8_NMODEL - 1]; P8XMixMap* d_xmaps = nullptr;
+  std::vector<const void*> jpg_blocks;   // the P8JpgDev blocks of the image models' lanes (they hold device pointers: cmx_p8stage_state_view)
   int last_byte = 0;                    // the last whole byte of the stream
   uint64_t image_chunks = 0;
   Staging st[P8S_BUFS];
@@ -1348,6 +1351,9 @@ cmx_p8stage_t* cmx_p8stage_create(int device) {
     h->d_mix = dev_copy(S->mix, h->pol);
     for (int m = 0; m < P8_NMODEL - 1; m++)
       if (h->L.xl[m].nx) { h->d_xfam[m] = dev_copy(S->xfam[m], h->pol); h->d_xlanes[m] = dev_copy(S->xlanes[m], h->pol); h->xview[m] = S->xview[m]; }
+    for (int m = 0; m < P8_NMODEL - 1; m++)
+      for (int l = 0; l < S->xlanes[m].nlanes; l++)
+        if (S->xlanes[m].lane[l].q.kind == P8L_JPG && S->xlanes[m].lane[l].jpg) h->jpg_blocks.push_back(S->xlanes[m].lane[l].jpg);
     {
       std::vector<P8XMixMap> mm(P8_NMODEL - 1);
       for (int m = 0; m < P8_NMODEL - 1; m++) {
@@ -1780,6 +1786,93 @@ int cmx_p8stage_role_ms(cmx_p8stage_t* h, double ms[7], uint64_t* chunks, int re
   *chunks = h->role_chunks;
   if (reset) { for (double& v : h->role_ms) v = 0; h->role_chunks = 0; }
   return 0;
+}
+
+}  // extern "C"
+
+// ---- the state view (cmx_p8stage_state_digest, cmx_p8stage_debug_layout, cmx_p8stage_debug_state_words) ----
+// Everything p8b::build_stage and cmx_p8stage_create ask the policy for is one list of blocks. Two kinds:
+//   the ROLE STRUCTS  P8CmDev (family), P8Cm2Dev x 3, P8LanesDev, P8DmcDev, P8MixDev, P8TailDev, per image model its P8CmDev and P8XLanesDev, and the
+//                     P8JpgDev of a JPEG lane: they hold device pointers, which differ from handle to handle and from run to run. They are read back,
+//                     every 8-byte word that is an address inside one of the handle's blocks is zeroed, and what is left -- the scalar words: the
+//                     registers between chunks, counters, offsets, last bits -- is region 9, digested on the host;
+//   the TABLES        every other block, digested where it lies. A table's region is the role whose struct points to it (the first in the order
+//                     above: stretch / nex / ilog are shared): 0 family (with P8FamHome), 1 ContextMap2, 2 the lanes' learners, 3 the DMC forest,
+//                     4 the 1552 x 28 mixer, 5 tail / APM, 6 the image models' families, 7 the image models' lanes, 8 the rest (the image models'
+//                     mixer maps). Inside a region: build order. A block is 64 zero bytes longer than asked for; the words asked for are covered.
+// Left out, no model state: d_x, d_order, d_prx, the staging buffers, h_mixfail, d_prof and the Late slots (none of them is policy memory).
+int cmx_p8stage_state_view(cmx_p8stage* h, std::vector<CmxStateRegion>& arrays, std::vector<uint32_t>& words, int* device) {
+  if (!h || !device) { cmx_set_err("cmx_p8stage_state_view: bad argument"); return 1; }
+  const std::vector<void*>& B = h->pol.blocks;
+  const std::vector<size_t>& Z = h->pol.sizes;
+  const int nb = (int)B.size();
+  if (Z.size() != B.size()) { cmx_set_err("cmx_p8stage_state_view: internal layout error"); return 1; }
+  auto block_of = [&](uint64_t v) {   // the block an address lies in, or -1
+    for (int i = 0; i < nb; i++) if (v >= (uint64_t)(uintptr_t)B[i] && v < (uint64_t)(uintptr_t)B[i] + Z[i] + 64) return i;
+    return -1;
+  };
+  struct Role { const void* p; int region; };
+  std::vector<Role> roles;
+  roles.push_back({h->d_fam, 0});
+  for (int k = 0; k < P8_NCM2; k++) roles.push_back({h->d_cm2[k], 1});
+  roles.push_back({h->d_lanes, 2}); roles.push_back({h->d_dmc, 3}); roles.push_back({h->d_mix, 4}); roles.push_back({h->d_tail, 5});
+  for (int m = 0; m < P8_NMODEL - 1; m++) if (h->d_xfam[m]) roles.push_back({h->d_xfam[m], 6});
+  for (int m = 0; m < P8_NMODEL - 1; m++) if (h->d_xlanes[m]) roles.push_back({h->d_xlanes[m], 7});
+  for (const void* j : h->jpg_blocks) roles.push_back({j, 7});
+  std::vector<int> region((size_t)nb, -1);
+  std::vector<char> is_role((size_t)nb, 0);
+  for (const Role& r : roles) {
+    const int i = r.p ? block_of((uint64_t)(uintptr_t)r.p) : -1;
+    if (i < 0 || B[i] != r.p) { cmx_set_err("cmx_p8stage_state_view: internal layout error"); return 1; }
+    is_role[i] = 1;
+  }
+  if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_p8stage_state_view: device error"); return 1; }
+  {
+    const int i = block_of((uint64_t)(uintptr_t)h->d_fam_home);
+    if (i >= 0 && !is_role[i]) region[i] = 0;
+  }
+  words.clear();
+  std::vector<uint64_t> buf;
+  for (const Role& r : roles) {
+    const int i = block_of((uint64_t)(uintptr_t)r.p);
+    buf.assign((Z[i] + 7) / 8, 0);   // (the block's zero tail makes the last partial word whole)
+    if (hipMemcpy(buf.data(), r.p, buf.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); cmx_set_err("cmx_p8stage_state_view: device error"); return 1; }
+    for (uint64_t& v : buf) {
+      const int j = v ? block_of(v) : -1;
+      if (j < 0) continue;
+      if (!is_role[j] && region[j] < 0) region[j] = r.region;
+      v = 0;   // a device address
+    }
+    const uint32_t* w = (const uint32_t*)buf.data();
+    words.insert(words.end(), w, w + buf.size() * 2);
+  }
+  arrays.clear();
+  for (int r = 0; r <= 8; r++)
+    for (int i = 0; i < nb; i++)
+      if (!is_role[i] && (region[i] < 0 ? 8 : region[i]) == r) arrays.push_back({(uint32_t*)B[i], (Z[i] + 3) / 4, r});
+  *device = h->device;
+  return 0;
+}
+
+extern "C" {
+
+static int p8_digest(const char* who, cmx_p8stage_t* h, uint64_t* out, size_t cap, int layout) {
+  if (!h) { cmx_set_err(std::string(who) + ": null handle"); return -1; }
+  if (h->failed) { cmx_set_err(std::string(who) + ": the stage failed earlier on this stream"); return -1; }
+  std::vector<CmxStateRegion> a; std::vector<uint32_t> w; int dev = 0;
+  if (cmx_p8stage_state_view(h, a, w, &dev)) return -1;
+  return cmx_state_digest_stage(who, dev, a.data(), (int)a.size(), &w, 9, out, cap, layout);
+}
+int cmx_p8stage_state_digest(cmx_p8stage_t* h, uint64_t* out, size_t cap) { return p8_digest("cmx_p8stage_state_digest", h, out, cap, 0); }
+int cmx_p8stage_debug_layout(cmx_p8stage_t* h, uint64_t* out, size_t cap) { return p8_digest("cmx_p8stage_debug_layout", h, out, cap, 1); }
+int cmx_p8stage_debug_state_words(cmx_p8stage_t* h, uint32_t* out, size_t cap) {
+  if (!h) { cmx_set_err("cmx_p8stage_debug_state_words: null handle"); return -1; }
+  std::vector<CmxStateRegion> a; std::vector<uint32_t> w; int dev = 0;
+  if (cmx_p8stage_state_view(h, a, w, &dev)) return -1;
+  if (!out) return (int)w.size();
+  if (cap < w.size()) { cmx_set_err("cmx_p8stage_debug_state_words: out[] is too small (" + std::to_string(w.size()) + " words)"); return -1; }
+  memcpy(out, w.data(), w.size() * 4);
+  return (int)w.size();
 }
 
 }  // extern "C"

@@ -237,7 +237,16 @@ struct cmx_pipeline {
   uint64_t jr_folded = 0;        // chunks whose partial records the host has folded (in stream order)
   std::string jr_path;           // cmx_pipeline_journal_write_files: where, and how many blocks are there already
   uint64_t jr_written = 0;
+  int sj_every = 0;              // cmx_pipeline_set_state_journal (0 = off: nothing below is used, nothing is launched or waited for)
+  uint64_t sj_bytes = 0;         // stream bytes of the chunks finished so far
+  uint64_t sj_upto = 0;          // chunks the last record covers
+  size_t sj_cols = 0;            // columns of a record (fixed by the first one)
+  std::vector<uint64_t> sj_rec;  // the records: a byte position and sj_cols digests each
+  std::string sj_path;           // cmx_pipeline_state_journal_write_file: where, and how many records are there already
+  uint64_t sj_written = 0;
+  bool sj_header = false;        // the file exists and has its header lines
 };
+static int state_journal_record(cmx_pipeline* h);
 
 namespace {
 // ---- the four kinds of shadow stages (pipeline_shadow.h), in ShadowId's order ----
@@ -1043,6 +1052,10 @@ static int finish_impl(cmx_pipeline_t* h, const float* cols, int first_col, int 
   h->finished++;
   if (h->hinted < h->finished) h->hinted = h->finished;  // hints nobody asked for are skipped
   txn.ok = true;
+  if (h->sj_every) {   // the state journal: after every sj_every-th chunk, once no begun chunk is waiting for its finish
+    h->sj_bytes += s.n;
+    if (h->finished == h->chunks && h->finished % (uint64_t)h->sj_every == 0 && state_journal_record(h)) return 1;
+  }
   return 0;
 }
 
@@ -1185,6 +1198,145 @@ int cmx_pipeline_journal_write_files(cmx_pipeline_t* h, const char* path, int fi
   h->jr_path = path;
   h->jr_written = upto;
   return 0;
+}
+
+// ---- the state digest and the state journal (include/cmix_amd.h, "State digest"; cmx_state_digest.h) ----
+namespace {
+// the stages in the order of a record's columns; a stage that is not enabled has none
+struct SjStage { int id; void* x; int (*digest)(void*, uint64_t*, size_t); int (*layout)(void*, uint64_t*, size_t); };
+void sj_stages(cmx_pipeline* h, std::vector<SjStage>& v) {
+  v.push_back({0, h->mix, [](void* x, uint64_t* o, size_t c) { return cmx_mixnet_state_digest((cmx_mixnet_t*)x, o, c); },
+               [](void* x, uint64_t* o, size_t c) { return cmx_mixnet_state_digest_layout((cmx_mixnet_t*)x, o, c); }});
+  v.push_back({1, h->ctx, [](void* x, uint64_t* o, size_t c) { return cmx_ctxmodels_state_digest((cmx_ctxmodels_t*)x, o, c); },
+               [](void* x, uint64_t* o, size_t c) { return cmx_ctxmodels_state_digest_layout((cmx_ctxmodels_t*)x, o, c); }});
+  v.push_back({2, h->lstm, [](void* x, uint64_t* o, size_t c) { return cmx_lstm_state_digest((cmx_lstm_t*)x, o, c); },
+               [](void* x, uint64_t* o, size_t c) { return cmx_lstm_state_digest_layout((cmx_lstm_t*)x, o, c); }});
+  if (h->fxcm) v.push_back({3, h->fxcm, [](void* x, uint64_t* o, size_t c) { return cmx_fxcm_state_digest((cmx_fxcm_t*)x, o, c); },
+                            [](void* x, uint64_t* o, size_t c) { return cmx_fxcm_state_digest_layout((cmx_fxcm_t*)x, o, c); }});
+  if (h->p8) v.push_back({4, h->p8, [](void* x, uint64_t* o, size_t c) { return cmx_p8stage_state_digest((cmx_p8stage_t*)x, o, c); },
+                          [](void* x, uint64_t* o, size_t c) { return cmx_p8stage_debug_layout((cmx_p8stage_t*)x, o, c); }});
+}
+int sj_guard(cmx_pipeline* h, const char* who) {
+  if (!h) { cmx_set_err(std::string(who) + ": null handle"); return 1; }
+  if (h->late) { cmx_set_err(std::string(who) + ": a handle that decodes is not covered (its kernels are resident and the stream has no rest point)"); return 1; }
+  if (h->failed) { cmx_set_err(std::string(who) + ": an earlier chunk of this handle failed part-way; its state is void (destroy it)"); return 1; }
+  if (h->finished != h->chunks) { cmx_set_err(std::string(who) + ": a begun chunk is waiting for cmx_pipeline_finish (the state is at rest between chunks only)"); return 1; }
+  return 0;
+}
+}  // namespace
+
+int cmx_pipeline_state_digest(cmx_pipeline_t* h, uint64_t* out, size_t cap) {
+  if (sj_guard(h, "cmx_pipeline_state_digest")) return -1;
+  if (out && cmx_pipeline_sync(h)) return -1;
+  size_t k = 0;
+  std::vector<SjStage> stages;
+  sj_stages(h, stages);
+  for (const SjStage& S : stages) {
+    const int n = S.digest(S.x, out ? out + k : nullptr, out ? (cap > k ? cap - k : 0) : 0);
+    if (n < 0) return -1;
+    k += (size_t)n;
+  }
+  return (int)k;
+}
+
+int cmx_pipeline_state_layout(cmx_pipeline_t* h, uint64_t* out, size_t cap) {
+  if (sj_guard(h, "cmx_pipeline_state_layout")) return -1;
+  size_t k = 0;
+  std::vector<uint64_t> t;
+  std::vector<SjStage> stages;
+  sj_stages(h, stages);
+  for (const SjStage& S : stages) {
+    const int n = S.layout(S.x, nullptr, 0);
+    if (n < 0) return -1;
+    if (out) {
+      if (cap < 4 * (k + (size_t)n)) { cmx_set_err("cmx_pipeline_state_layout: out[] is too small (four words per column)"); return -1; }
+      t.resize(3 * (size_t)n);
+      if (S.layout(S.x, t.data(), t.size()) != n) return -1;
+      for (int i = 0; i < n; ++i) { uint64_t* o = out + 4 * (k + i); o[0] = (uint64_t)S.id; o[1] = t[3 * i]; o[2] = t[3 * i + 1]; o[3] = t[3 * i + 2]; }
+    }
+    k += (size_t)n;
+  }
+  return (int)k;
+}
+
+int cmx_pipeline_set_state_journal(cmx_pipeline_t* h, int every_chunks) {
+  if (sj_guard(h, "cmx_pipeline_set_state_journal")) return 1;
+  if (every_chunks < 0) { cmx_set_err("cmx_pipeline_set_state_journal: every_chunks must be 0 (off) or a number of chunks"); return 1; }
+  if (h->chunks) { cmx_set_err("cmx_pipeline_set_state_journal: only before the first chunk"); return 1; }
+  h->sj_every = every_chunks;
+  return 0;
+}
+
+static int state_journal_flush(cmx_pipeline* h);
+// one record: the state after every chunk finished so far
+static int state_journal_record(cmx_pipeline* h) {
+  if (!h->sj_cols) {
+    const int n = cmx_pipeline_state_digest(h, nullptr, 0);
+    if (n <= 0) return 1;
+    h->sj_cols = (size_t)n;
+  }
+  const size_t at = h->sj_rec.size();
+  h->sj_rec.resize(at + 1 + h->sj_cols);
+  h->sj_rec[at] = h->sj_bytes;
+  if (cmx_pipeline_state_digest(h, h->sj_rec.data() + at + 1, h->sj_cols) != (int)h->sj_cols) { h->sj_rec.resize(at); return 1; }
+  h->sj_upto = h->finished;
+  return h->sj_path.empty() ? 0 : state_journal_flush(h);
+}
+
+int cmx_pipeline_state_journal_read(cmx_pipeline_t* h, uint64_t first, uint64_t n, uint64_t* out, uint64_t* nrecords, uint64_t* ncols) {
+  if (!h) { cmx_set_err("cmx_pipeline_state_journal_read: null handle"); return 1; }
+  if (!h->sj_every) { cmx_set_err("cmx_pipeline_state_journal_read: the state journal is off (cmx_pipeline_set_state_journal)"); return 1; }
+  const uint64_t have = h->sj_cols ? h->sj_rec.size() / (1 + h->sj_cols) : 0;
+  if (nrecords) *nrecords = have;
+  if (ncols) *ncols = h->sj_cols;
+  if (!n) return 0;
+  if (!out || first > have || n > have - first) { cmx_set_err("cmx_pipeline_state_journal_read: no such records"); return 1; }
+  memcpy(out, h->sj_rec.data() + first * (1 + h->sj_cols), n * (1 + h->sj_cols) * 8);
+  return 0;
+}
+
+// the records not yet in the file; the first call creates (or empties) it and writes the header lines that carry the layout
+static int state_journal_flush(cmx_pipeline* h) {
+  if (!h->sj_cols) {
+    const int n = cmx_pipeline_state_digest(h, nullptr, 0);
+    if (n <= 0) return 1;
+    h->sj_cols = (size_t)n;
+  }
+  const size_t w = 1 + h->sj_cols;
+  const uint64_t have = h->sj_rec.size() / w;
+  const bool fresh = !h->sj_header;
+  if (!fresh && have == h->sj_written) return 0;
+  FILE* f = fopen(h->sj_path.c_str(), fresh ? "w" : "a");
+  if (!f) { cmx_set_err("state journal: cannot open " + h->sj_path); return 1; }
+  h->sj_header = true;
+  if (fresh) {
+    std::vector<uint64_t> lay(4 * h->sj_cols);
+    if (cmx_pipeline_state_layout(h, lay.data(), lay.size()) != (int)h->sj_cols) { fclose(f); return 1; }
+    fprintf(f, "# cmix_amd state journal 1\n# columns %zu\n", h->sj_cols);
+    for (size_t c = 0; c < h->sj_cols; ++c)
+      fprintf(f, "# col %zu %llu %llu %llu %llu\n", c, (unsigned long long)lay[4 * c], (unsigned long long)lay[4 * c + 1], (unsigned long long)lay[4 * c + 2], (unsigned long long)lay[4 * c + 3]);
+  }
+  for (uint64_t r = h->sj_written; r < have; ++r) {
+    const uint64_t* p = h->sj_rec.data() + r * w;
+    fprintf(f, "%llu", (unsigned long long)p[0]);
+    for (size_t c = 1; c < w; ++c) fprintf(f, " %016llx", (unsigned long long)p[c]);
+    fputc('\n', f);
+  }
+  const bool bad = fflush(f) != 0 || ferror(f);
+  if (fclose(f) != 0 || bad) { cmx_set_err("state journal: write error on " + h->sj_path); return 1; }
+  h->sj_written = have;
+  return 0;
+}
+
+int cmx_pipeline_state_journal_write_file(cmx_pipeline_t* h, const char* path, int final) {
+  if (!h || !path || !path[0]) { cmx_set_err("cmx_pipeline_state_journal_write_file: bad argument"); return 1; }
+  if (!h->sj_every) { cmx_set_err("cmx_pipeline_state_journal_write_file: the state journal is off (cmx_pipeline_set_state_journal)"); return 1; }
+  if (!h->sj_path.empty() && h->sj_path != path) { cmx_set_err("cmx_pipeline_state_journal_write_file: this handle's state journal is being written to " + h->sj_path); return 1; }
+  if (final && h->sj_upto < h->finished) {   // the record after the last chunk
+    if (sj_guard(h, "cmx_pipeline_state_journal_write_file") || state_journal_record(h)) return 1;
+  }
+  h->sj_path = path;
+  return state_journal_flush(h);
 }
 
 // ---- repair on the majority (include/cmix_amd.h, cmx_pipeline_set_shadow_repair) ----
@@ -1470,6 +1622,7 @@ int cmx_pipeline_late_start(cmx_pipeline_t* h, int last_bit) {
   if (!h->fxcm || !h->p8) { cmx_set_err("cmx_pipeline_late_start: enable the fxcm and paq8 stages first (a decoder takes no columns from the caller)"); return 1; }
   if (h->chunks) { cmx_set_err("cmx_pipeline_late_start: the handle has coded chunks of known bytes (a stream is decoded from its first bit)"); return 1; }
   if (h->compact) { cmx_set_err("cmx_pipeline_late_start: the stages share HIP streams (CMX_PIPELINE_STREAMS); a decoder needs every stage kernel running at once"); return 1; }
+  if (h->sj_every) { cmx_set_err("cmx_pipeline_late_start: the state journal is on (cmx_pipeline_set_state_journal); it does not cover a decoder, whose kernels are resident and whose stream has no rest point"); return 1; }
   if (hipSetDevice(h->device) != hipSuccess) { cmx_set_err("hipSetDevice failed"); return 1; }
   if (hipDeviceSynchronize() != hipSuccess) { cmx_set_err("cmx_pipeline_late_start: device error"); return 1; }   // pretraining is complete
   for (ShadowId k : kShadowLast) shadow_drop(h, kShadow[k]);   // a decoder is not covered by the vote (include/cmix_amd.h): it holds no stream, workgroup or buffer of it

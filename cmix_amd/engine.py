@@ -260,6 +260,23 @@ def lib():
         L.cmx_set_journal_check.argtypes = [C.c_void_p, C.c_char_p]
         L.cmx_journal_write_files.argtypes = [C.c_void_p, C.c_char_p]
         L.cmx_journal_close_files.argtypes = [C.c_void_p]
+        L.cmx_state_digest_host.restype = C.c_uint64
+        L.cmx_state_digest_host.argtypes = [C.c_void_p, C.c_uint64]
+        L.cmx_state_digest_arrays.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        for st in ("mixnet", "ctxmodels", "lstm", "fxcm"):
+            getattr(L, "cmx_%s_state_digest" % st).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            getattr(L, "cmx_%s_state_digest_layout" % st).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_p8stage_state_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_p8stage_debug_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_p8stage_debug_state_words.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_pipeline_state_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_pipeline_state_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cmx_pipeline_set_state_journal.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_pipeline_state_journal_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cmx_pipeline_state_journal_write_file.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        L.cmx_set_state_journal.argtypes = [C.c_void_p, C.c_int]
+        L.cmx_state_journal_write_file.argtypes = [C.c_void_p, C.c_char_p]
+        L.cmx_state_journal_close.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -646,6 +663,47 @@ def journal_host_digest(p, bits, stream_bit0=0, log2=19):
     return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
 
 
+def state_digest_host(words):
+    """cmx_state_digest_host: the state digest (include/cmix_amd.h, "State digest") of HOST 32-bit words, in plain C++ (no device)."""
+    w = np.ascontiguousarray(words).view(np.uint32).ravel()
+    return int(lib().cmx_state_digest_host(w.ctypes.data if len(w) else None, len(w)))
+
+
+def state_digest_arrays(tensors, device=0):
+    """cmx_state_digest_arrays: the digests of a list of cuda tensors (4-byte elements, contiguous, each an allocation of its own) in ONE launch."""
+    n = len(tensors)
+    ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() if t.numel() else None for t in tensors])
+    words = np.array([t.numel() for t in tensors], np.uint64)
+    assert all(t.is_cuda and t.element_size() == 4 and t.is_contiguous() for t in tensors)
+    out = np.zeros(max(n, 1), np.uint64)
+    if lib().cmx_state_digest_arrays(device, ptrs, words.ctypes.data, n, out.ctypes.data):
+        raise CmxError(last_error())
+    return out[:n]
+
+
+def _state_digest(fn, h, per=1):
+    """one of the cmx_*_state_digest / _layout calls: `per` words per column"""
+    n = fn(h, None, 0)
+    if n < 0:
+        raise CmxError(last_error())
+    out = np.zeros(max(n, 1) * per, np.uint64)
+    if fn(h, out.ctypes.data, len(out)) != n:
+        raise CmxError(last_error())
+    return out[:n * per].reshape(n, per) if per > 1 else out[:n]
+
+
+class _StateDigest:
+    """state_digest() / state_digest_layout() of a stage handle (include/cmix_amd.h, "State digest"): one 64-bit digest per state array and a last one
+    over the words the stage's state_diff compares on the host; the layout gives (region, word offset inside the region, words) per column."""
+    _sd = None   # the stage's name in the C ABI
+
+    def state_digest(self):
+        return _state_digest(getattr(lib(), "cmx_%s_state_digest" % self._sd), self.h)
+
+    def state_digest_layout(self):
+        return _state_digest(getattr(lib(), "cmx_%s_debug_layout" % self._sd if self._sd == "p8stage" else "cmx_%s_state_digest_layout" % self._sd), self.h, 3)
+
+
 class Journal:
     """The stand-alone stream journal (include/cmix_amd.h, cmx_journal_*): per-block digests of rows, selectors, bits and p on the device."""
 
@@ -697,8 +755,10 @@ class Journal:
             pass
 
 
-class MixNet:
+class MixNet(_StateDigest):
     """Final mixing network stage (layers 0-2 + SSE) of one stream on one GPU."""
+
+    _sd = "mixnet"
 
     def __init__(self, device=0):
         self.h = lib().cmx_mixnet_create(device)
@@ -839,9 +899,11 @@ class MixNet:
         return {"mid_hits": int(out[0]), "serial_halves": int(out[1])}
 
 
-class Lstm:
+class Lstm(_StateDigest):
     """Byte-level LSTM byte mixer stage of one stream on one GPU (chunk mode)."""
     SKIP_RAND = 31
+
+    _sd = "lstm"
 
     def __init__(self, vocab, device=0, skip_rand=SKIP_RAND):
         vocab = np.ascontiguousarray(vocab, np.uint8)
@@ -917,8 +979,10 @@ class Lstm:
 SMALL_COLS = [0, 1, 2] + list(range(2025, 2076))  # layer-0 columns the ctx/small-model stage writes
 
 
-class CtxModels:
+class CtxModels(_StateDigest):
     """Context plumbing + the 54 small native models of one stream on one GPU (chunk mode)."""
+
+    _sd = "ctxmodels"
 
     def __init__(self, vocab, device=0, compact=False):
         """compact=True: model l writes column l of a [8N, >= 64] matrix (include/cmix_amd.h, cmx_ctxmodels_create_compact); the state is the same"""
@@ -1225,6 +1289,35 @@ class Pipeline(_Shadows):
     def journal_write_files(self, path, final=False):
         """Append the blocks completed since the last call to `path` and `path.inputs` (final: the partial last block too, after sync())."""
         if lib().cmx_pipeline_journal_write_files(self.h, os.fsencode(path), int(bool(final))):
+            raise CmxError(last_error())
+
+    def state_digest(self):
+        """cmx_pipeline_state_digest: between chunks; sync, then every enabled stage's digests in the order mixnet, context, LSTM, fxcm, paq8."""
+        return _state_digest(lib().cmx_pipeline_state_digest, self.h)
+
+    def state_layout(self):
+        """cmx_pipeline_state_layout: per column (stage, region, word offset inside the region, words)."""
+        return _state_digest(lib().cmx_pipeline_state_layout, self.h, 4)
+
+    def set_state_journal(self, every_chunks=1):
+        """The state journal (include/cmix_amd.h, cmx_pipeline_set_state_journal): a record after every every_chunks-th chunk, 0 = off; before the first chunk."""
+        if lib().cmx_pipeline_set_state_journal(self.h, int(every_chunks)):
+            raise CmxError(last_error())
+
+    def state_journal(self):
+        """(layout [ncols, 4], byte positions [nrecords], words [nrecords, ncols]) of the records taken so far; cmix_amd.journal writes and compares them."""
+        n, c = C.c_uint64(0), C.c_uint64(0)
+        if lib().cmx_pipeline_state_journal_read(self.h, 0, 0, None, C.byref(n), C.byref(c)):
+            raise CmxError(last_error())
+        lay = self.state_layout()
+        rec = np.zeros((n.value, 1 + len(lay)), np.uint64)
+        if n.value and (c.value != len(lay) or lib().cmx_pipeline_state_journal_read(self.h, 0, n.value, rec.ctypes.data, None, None)):
+            raise CmxError(last_error())
+        return lay, rec[:, 0].copy(), rec[:, 1:].copy()
+
+    def state_journal_write_file(self, path, final=False):
+        """From now on every record goes to `path` as it is taken (final: the record after the last chunk first, if the period has not taken it)."""
+        if lib().cmx_pipeline_state_journal_write_file(self.h, os.fsencode(path), int(bool(final))):
             raise CmxError(last_error())
 
     def set_shadow_repair(self, max_repairs):
@@ -1621,6 +1714,15 @@ class Predictor(_Shadows):
         if lib().cmx_set_journal(self.h, int(log2)):
             raise CmxError(last_error())
 
+    def set_state_journal(self, every_chunks=1, path=None):
+        """The state journal of a look-ahead compressor (include/cmix_amd.h, cmx_set_state_journal): a record after every every_chunks-th chunk to `path`."""
+        if lib().cmx_set_state_journal(self.h, int(every_chunks)) or (path is not None and lib().cmx_state_journal_write_file(self.h, os.fsencode(path))):
+            raise CmxError(last_error())
+
+    def state_journal_close(self):
+        if lib().cmx_state_journal_close(self.h):
+            raise CmxError(last_error())
+
     def set_journal_check(self, path):
         """A decoder only: hold the decode to a compressor's journal (`path`, `path.inputs`); Perceive raises at the first block that differs."""
         if lib().cmx_set_journal_check(self.h, os.fsencode(path)):
@@ -1663,9 +1765,11 @@ class Predictor(_Shadows):
 
 
 
-class Fxcm:
+class Fxcm(_StateDigest):
     """The fxcm stage of one stream on one GPU (chunk mode): layer-0 columns 3..433. The text parser half runs on the
     calling thread inside run(); the learned tables live on the device (include/cmix_amd.h section 2f)."""
+
+    _sd = "fxcm"
 
     def __init__(self, dictionary_path=None, device=0, shadow=False):
         """shadow=True: a shadow instance (cmx_fxcm_create_shadow) -- the same device state, no parser and no dictionary; run_shared() only"""
@@ -1782,9 +1886,11 @@ class Fxcm:
         self._keep = []
 
 
-class P8Stage:
+class P8Stage(_StateDigest):
     """The paq8 stage of one stream on one GPU (include/cmix_amd.h section 2f): bytes in (host), per bit the 1591 values
     PAQ8::Predict() returns out (device)."""
+
+    _sd = "p8stage"
 
     def __init__(self, device=0):
         self.device = device
@@ -1810,6 +1916,16 @@ class P8Stage:
     def sync(self):
         if lib().cmx_p8stage_sync(self.h):
             raise CmxError(last_error())
+
+    def debug_state_words(self):
+        """The scalar words of the role structs, device addresses zeroed: what the digest's last column covers (cmx_p8stage_debug_state_words)."""
+        n = lib().cmx_p8stage_debug_state_words(self.h, None, 0)
+        if n < 0:
+            raise CmxError(last_error())
+        out = np.zeros(max(n, 1), np.uint32)
+        if lib().cmx_p8stage_debug_state_words(self.h, out.ctypes.data, len(out)) != n:
+            raise CmxError(last_error())
+        return out[:n]
 
     def debug_set_pos(self, pos):
         """Test hook (before the first byte): the front end's byte position (the index into paq8's 2^30-byte history ring)."""

@@ -59,7 +59,7 @@ class EngineStream:
     is for a compressor (reference src/predictor.cpp:361-469), a sub-chunk of known bytes at a time. feed() enqueues;
     finish() returns the container bytes (header + arithmetic code), identical to the reference binary's file."""
 
-    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0, repair=0, ctx_shadow=0, journal=0, lstm_shadow=0, fxcm_shadow=0):
+    def __init__(self, device_index, stream, sub_chunk=4096, dictionary_used=False, vocab=None, verify=False, shadow=0, repair=0, ctx_shadow=0, journal=0, lstm_shadow=0, fxcm_shadow=0, state_journal=0):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", device_index)
@@ -93,6 +93,9 @@ class EngineStream:
             self.pipe.set_fxcm_shadow(fxcm_shadow)
         if journal:   # per-block digests of every sub-chunk's rows, selectors, bits and p, blocks of 2^journal bits (cmx_pipeline_set_journal): journal()
             self.pipe.set_journal(19 if journal is True else int(journal))
+        self.state_journal_every = int(state_journal)
+        if state_journal:   # one record of every device stage's state digests after every state_journal-th sub-chunk and after the last (cmx_pipeline_set_state_journal): state_journal()
+            self.pipe.set_state_journal(self.state_journal_every)
         self.waited = 0
         self.pos = 0
         self.nsub = 0
@@ -126,6 +129,16 @@ class EngineStream:
             return self.header + enc.data()
         finally:
             enc.close()
+
+    def state_journal(self):
+        """(layout, byte positions, words) of the stream's state journal (cmix_amd.journal writes and compares them); complete after finish()."""
+        if self.state_journal_every and self.nsub % self.state_journal_every:   # the record after the last sub-chunk
+            self.pipe.sync()
+            lay, pos, words = self.pipe.state_journal()
+            if not len(pos) or pos[-1] != self.pos:
+                return lay, np.append(pos, np.uint64(self.pos)), np.vstack([words, self.pipe.state_digest()[None, :]])
+            return lay, pos, words
+        return self.pipe.state_journal()
 
     def journal(self):
         """(ends, words) of the stream's journal (cmix_amd.journal writes and compares them); complete after finish()."""

@@ -159,6 +159,18 @@ int cmx_fxcm_shadow_report(cmx_t*, uint64_t out[8]);
  * partial last block, the block count -- can only be printed to stderr, so a program that wants it as an error calls cmx_journal_close_files first,
  * as integration/predictor_dropin.h does). With none of the three set nothing changes. */
 int cmx_set_journal(cmx_t*, int log2_block_bits);
+/* The STATE JOURNAL of a cmx_t (section "State digest" below; cmx_pipeline_set_state_journal has the record and the file's form): a compressor's handle
+ * in look-ahead mode (cmx_stage_input) takes one record of every device stage's state digests after every every_chunks-th chunk of 4096 bytes and after
+ * the last (0 = off, the default; before the first cmx_stage_input / cmx_predict). _write_file names the file the records go to as they are taken;
+ * _close (cmx_destroy makes the call if the program has not) writes the record after the last chunk. A handle that takes its columns from the caller
+ * has no pipeline and takes no records. A DECODER is not covered: cmx_predict fails with a message if the switch was set by cmx_set_state_journal.
+ * ENVIRONMENT: cmx_create reads CMIX_STATE_JOURNAL=path [CMIX_STATE_JOURNAL_EVERY=n, default CMX_STATE_JOURNAL_EVERY] where it reads CMIX_JOURNAL; it
+ * is a file of its own (`path` and `path.inputs` of the stream journal keep their form). A decoder created under it says on stderr that it is not
+ * covered and decodes as before. */
+#define CMX_STATE_JOURNAL_EVERY 256   /* chunks of 4096 bytes: a record per MiB, the smallest measured period with no cost resolved per stream (profiles/r21_state_journal.txt) */
+int cmx_set_state_journal(cmx_t*, int every_chunks);
+int cmx_state_journal_write_file(cmx_t*, const char* path);
+int cmx_state_journal_close(cmx_t*);
 int cmx_set_journal_check(cmx_t*, const char* path);
 int cmx_journal_write_files(cmx_t*, const char* path);
 int cmx_journal_close_files(cmx_t*);
@@ -892,6 +904,26 @@ int cmx_pipeline_mixnet_mode(cmx_pipeline_t*);
 int cmx_pipeline_set_journal(cmx_pipeline_t*, int log2_block_bits);
 int cmx_pipeline_journal_read(cmx_pipeline_t*, uint64_t first, uint64_t n, uint64_t* out, uint64_t* nblocks);
 int cmx_pipeline_journal_write_files(cmx_pipeline_t*, const char* path, int final);
+/* STATE DIGEST and STATE JOURNAL (section "State digest" below; opt-in). _state_digest: between chunks only (a begun chunk must have been finished);
+ * cmx_pipeline_sync first -- after a sync that follows the submit of chunk c every stage's state is the state after chunk c -- then every enabled
+ * stage's digest in the fixed order mixnet, context, LSTM, fxcm, paq8 into out[cap]; returns the number of columns (out == NULL: only that), -1 on
+ * error. The shadows' state is not digested, only the stream's own. _state_layout: per column four words -- stage (0 mixnet, 1 context, 2 LSTM,
+ * 3 fxcm, 4 paq8), region, word offset inside the region, words -- into out[cap] (cap >= 4 * columns); returns the number of columns.
+ * _set_state_journal (every_chunks = 0 off, the default: the handle queues exactly the launches it queues without it; before the first chunk):
+ * after every every_chunks-th finished chunk one record -- the stream's byte position, then one digest per column -- is taken (a sync and a read of
+ * the whole state: the chunks in flight drain first). Coexists with verify, the shadow votes, repair, the stream journal and tolerance mode.
+ * _state_journal_read: *nrecords / *ncols (either may be NULL) = records taken so far / columns; out receives records first .. first + n - 1 of
+ * 1 + columns words. _state_journal_write_file: from this call on every record is appended to `path` (created or emptied by the first call,
+ * which also writes the header lines that carry the layout) and flushed as it is taken, so that a run killed at a time limit leaves its records;
+ * final != 0 (after the last chunk) first takes the record after the last chunk if the period has not. The file: lines "# cmix_amd state journal 1",
+ * "# columns N", N lines "# col k stage region offset words", then per record "<byte position> <N words of 16 hex digits>" (cmix_amd/journal.py reads
+ * and compares them: python -m cmix_amd.journal state-diff a b). A handle that decodes is refused by all of them, and cmx_pipeline_late_start
+ * refuses a handle whose state journal is on: the decoder's kernels are resident and its stream has no rest point. */
+int cmx_pipeline_state_digest(cmx_pipeline_t*, uint64_t* out, size_t cap);
+int cmx_pipeline_state_layout(cmx_pipeline_t*, uint64_t* out, size_t cap);
+int cmx_pipeline_set_state_journal(cmx_pipeline_t*, int every_chunks);
+int cmx_pipeline_state_journal_read(cmx_pipeline_t*, uint64_t first, uint64_t n, uint64_t* out, uint64_t* nrecords, uint64_t* ncols);
+int cmx_pipeline_state_journal_write_file(cmx_pipeline_t*, const char* path, int final);
 /* Predictor::Pretrain over n dictionary bytes (HOST pointer), before the first submit: only the stages holding
  * `models_` learn (today: contexts + small models); mixers, SSE, LSTM and PPMd are not trained (predictor.cpp:471-487). */
 int cmx_pipeline_pretrain(cmx_pipeline_t*, const uint8_t* bytes, size_t n);
@@ -931,6 +963,43 @@ int cmx_journal_blocks(cmx_journal_t*, uint64_t* nblocks);
 int cmx_journal_read(cmx_journal_t*, uint64_t first, uint64_t n, uint64_t* out);
 void cmx_journal_destroy(cmx_journal_t*);
 size_t cmx_journal_host_digest(const float* p, const uint8_t* bits, size_t nbits, uint64_t stream_bit0, int log2_block_bits, uint64_t* out);
+
+/* ------------------------------------------------------------------------
+ * State digest: one 64-bit word per state array of a device stage (cmix_amd/csrc/cmx_state_digest.h, state_digest.hip; cmix_amd/journal.py has the
+ * numpy model). For an array of n 32-bit words w[0..n), n < 2^32:
+ *     D = sum over i of splitmix64((uint64(i) << 32) | w[i])   (mod 2^64), splitmix64 as in the stream journal above
+ * The sum is order-independent (a parallel kernel is deterministic); splitmix64 is a bijection, so a change of one word w -> w' always changes D, by
+ * splitmix64(i, w') - splitmix64(i, w). An array of 2^32 words or more is refused (none exists today). What it is for: two runs' state, written down
+ * as they go (the state journal of a pipeline / a cmx_t), compared later -- "the first thing that differs is fxcm's wx after byte N".
+ * cmx_state_digest_host: the function on the CPU (HOST words). cmx_state_digest_arrays: the kernel on n DEVICE arrays (each 16-byte aligned, as every
+ * hipMalloc is; words[r] 32-bit words) in ONE launch; synchronises the device before and after; out[n]. 0, or 1 on error.
+ * cmx_<stage>_state_digest(handle, out, cap): synchronises, then one digest per state array of the handle, in the order of the stage's state list
+ * (mixnet: regions 0..9 of cmx_mixnet_state_diff; context: the arrays cmx_ctxmodels_state_diff walks, region-then-lane; LSTM and fxcm: the arrays of
+ * their _debug_layout; paq8: cmx_p8stage_debug_layout), then -- so that nothing the stage's _state_diff sees is invisible -- one last column over the
+ * words it compares on the host, digested with the same function: mixnet's scalar words (region 10), the LSTM's counters bytes_done, hc, bptt_rounds
+ * as six words (listed as region 11), fxcm's FxDev with its device pointers zeroed followed by bytes_done as two words (region 11); the context stage
+ * has none. Returns the number of columns (out == NULL: only that; 11, the context stage's arrays, 81, 141 and paq8's count), -1 on error.
+ * cmx_<stage>_state_digest_layout: per column (region, word offset inside the region's arrays laid end to end, words), three words each.
+ * paq8 (it has no _state_diff; this is its state list): every table p8b::build_stage allocates, by region 0 the ContextMap family with P8FamHome,
+ * 1 the three ContextMap2, 2 the lanes' learners, 3 the DMC forest, 4 the 1552 x 28 mixer, 5 tail / APM tables, 6 the image models' families, 7 the
+ * image models' lanes, 8 the image models' mixer maps; then region 9: the scalar words of the role structs (P8CmDev, P8Cm2Dev x 3, P8LanesDev,
+ * P8DmcDev, P8MixDev, P8TailDev, the image models' P8CmDev / P8XLanesDev / P8JpgDev) with every device address in them zeroed, digested on the host
+ * (cmx_p8stage_debug_state_words reads them: out == NULL returns their number). Left out, no model state: d_x, d_order, d_prx, staging, h_mixfail,
+ * d_prof, the Late slots. No table was found whose words depend on timing: two handles fed equal bytes, in one launch or in ragged ones, and a
+ * handle run under poisoned LDS agree in every column (tests/test_gpu_state_digest.py).
+ * NOT COVERED: the host stages' state (PPMd's arena, paq8's front end, fxcm's parser); pretraining as it runs (the first record after it covers its
+ * result); the decoder.
+ * ------------------------------------------------------------------------ */
+uint64_t cmx_state_digest_host(const uint32_t* words, uint64_t n);
+int cmx_state_digest_arrays(int device, const void* const* d_arrays, const uint64_t* words, int n, uint64_t* out);
+int cmx_mixnet_state_digest(cmx_mixnet_t*, uint64_t* out, size_t cap);
+int cmx_mixnet_state_digest_layout(cmx_mixnet_t*, uint64_t* out, size_t cap);
+int cmx_ctxmodels_state_digest(cmx_ctxmodels_t*, uint64_t* out, size_t cap);
+int cmx_ctxmodels_state_digest_layout(cmx_ctxmodels_t*, uint64_t* out, size_t cap);
+int cmx_lstm_state_digest(cmx_lstm_t*, uint64_t* out, size_t cap);
+int cmx_lstm_state_digest_layout(cmx_lstm_t*, uint64_t* out, size_t cap);
+int cmx_fxcm_state_digest(cmx_fxcm_t*, uint64_t* out, size_t cap);
+int cmx_fxcm_state_digest_layout(cmx_fxcm_t*, uint64_t* out, size_t cap);
 
 /* ------------------------------------------------------------------------
  * Device libm probes (parity tests): evaluate the engine's expf / tanhf /
@@ -979,6 +1048,10 @@ int cmx_p8stage_set_upload_stream(cmx_p8stage_t*, void* stream);   /* see cmx_mi
  * common path: out[8 bp + k] (k = 0 per-step values, 1 phase 1, 2 barrier, 3 run / rounds, 4 rest), out[64 + bp] steps in rounds,
  * out[72 + bp] instances walked, out[80 + bp] steps */
 int cmx_p8stage_profile(cmx_p8stage_t*, unsigned long long out128[128]);
+/* the stage's state digest, its layout and the scalar words of its last column (section "State digest" above) */
+int cmx_p8stage_state_digest(cmx_p8stage_t*, uint64_t* out, size_t cap);
+int cmx_p8stage_debug_layout(cmx_p8stage_t*, uint64_t* out, size_t cap);
+int cmx_p8stage_debug_state_words(cmx_p8stage_t*, uint32_t* out, size_t cap);
 
 
 /* ------------------------------------------------------------------------

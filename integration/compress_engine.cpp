@@ -65,6 +65,10 @@ void CompressEngine(Predictor* P, const std::vector<uint8_t>& data, cmx_encoder_
   for (size_t c = nchunks > R ? nchunks - R : 0; c < nchunks; ++c) drain(c);
   if (cmx_pipeline_sync(P->pipe())) Predictor::Die();
   if (journal && cmx_pipeline_journal_write_files(P->pipe(), journal, 1)) Predictor::Die();
+  {
+    const char* sj = getenv("CMIX_STATE_JOURNAL");   // (switched on in main): the record after the last chunk
+    if (sj && sj[0] && cmx_pipeline_state_journal_write_file(P->pipe(), sj, 1)) Predictor::Die();
+  }
   uint64_t rep[2 + CMX_REPAIR_LOG * CMX_REPAIR_WORDS];   // one line per repair on the majority (CMIX_SHADOW_REPAIR): none without an event
   if (cmx_pipeline_shadow_repairs(P->pipe(), rep, sizeof rep / sizeof rep[0])) Predictor::Die();
   for (uint64_t i = 0; i < rep[1]; ++i)
@@ -157,6 +161,11 @@ int main(int argc, char* argv[]) {
     const char* jr = getenv("CMIX_JOURNAL");
     const char* jl = getenv("CMIX_JOURNAL_LOG2");
     if (jr && jr[0] && cmx_pipeline_set_journal(p.pipe(), jl ? atoi(jl) : 19)) Predictor::Die();
+    // CMIX_STATE_JOURNAL=path [CMIX_STATE_JOURNAL_EVERY=n chunks]: one record of every device stage's state digests after every n-th chunk and after the last, to `path` (a
+    // file of its own) as the run goes
+    const char* sj = getenv("CMIX_STATE_JOURNAL");
+    const char* se = getenv("CMIX_STATE_JOURNAL_EVERY");
+    if (sj && sj[0] && (cmx_pipeline_set_state_journal(p.pipe(), se && se[0] ? atoi(se) : CMX_STATE_JOURNAL_EVERY) || cmx_pipeline_state_journal_write_file(p.pipe(), sj, 0))) Predictor::Die();
   }
   const double t_ready = since();
   if (enable_preprocess) preprocessor::Pretrain(&p, dictionary);

@@ -72,10 +72,13 @@ class Predictor {
     // run goes (-c: all 179 words per block, from the device; -d: the p and bits words, folded on this thread). CMIX_JOURNAL_CHECK=path (-d): the decode is held to a
     // compressor's journal block by block and stops at the first block whose p or bits word differs (the block size comes from that file). cmx_create reads the three
     // itself (the one switch the library takes from the environment: a journal works in a program whichever shim it was compiled against); Perceive writes as it goes.
+    // CMIX_STATE_JOURNAL=path [CMIX_STATE_JOURNAL_EVERY=n chunks]: cmx_create reads it at the same place. -c: one record of every device stage's state digests after every
+    // n-th chunk of 4096 bytes and after the last goes to `path` (a file of its own); -d: the decoder is not covered, says so on stderr and decodes as before.
   }
   ~Predictor() {
     // the rest of the journal, the partial last block included; with CMIX_JOURNAL_CHECK the last block and the block count are compared here (nothing without a journal)
     if (cmx_journal_close_files(h_)) Die();
+    if (cmx_state_journal_close(h_)) Die();   // the state journal's record after the last chunk (nothing without CMIX_STATE_JOURNAL)
     uint64_t rep[2 + CMX_REPAIR_LOG * CMX_REPAIR_WORDS];   // one line per repair on the majority: none without an event
     if (cmx_shadow_repairs(h_, rep, sizeof rep / sizeof rep[0]) == 0)
       for (uint64_t i = 0; i < rep[1]; ++i)
